@@ -1,8 +1,16 @@
 """Benchmark: vectorised gym-pybullet-adrp env.step throughput on N MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what `value` needs and nothing else: it sets up, runs W warm-up steps, times
+exactly K steps, writes the last timed step's outputs if `--dump-outputs DIR` is given (the
+arrays env.step returned: obs, reward, terminated, truncated, terminal_observation, as
+DIR/<name>.npy in float32; seeds are fixed, so the same arguments give the same inputs in every
+run and two builds can be compared array for array) and prints the JSON line.  `--full` adds
+everything else described below: the `configs` sub-records, the CPU baselines, the env-count sweep,
+the eager per-dispatch kernel times and end-to-end rate.
 
 `value` is BASELINE.json configs[1] (HoverAviary, 4096 envs x 1 drone per GPU, PYB, 240/30 Hz =
 8 sub-steps, RPM actions, auto-reset) at the reference's precision (float64 kernel; the
@@ -11,7 +19,7 @@ fused HIP launch per GPU, envs sharded across ranks (weak scaling, no collective
 path).  Inputs are resident in HBM before the timed region.  `--gpus N` without a launcher
 starts N ranks itself (a child `torch.distributed.run`), before anything touches the GPU.
 
-The same JSON line carries sub-records (`configs`), each timed the same way:
+With `--full` the same JSON line carries sub-records (`configs`), each timed the same way:
   config5      every N: MultiRaceAviary COMPETE level3, 4 drones x 4096 envs per GPU, PYB_DW,
                disturbances on (at N = 1 this is configs[3]), float64 physics + wrapper and
                float32 firmware as the reference; kernel-only, and (N > 1) step + RCCL
@@ -59,6 +67,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=2000)
     p.add_argument("--warmup", type=int, default=200)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: config sub-records, CPU baselines, the other "
+                        "precision, the env-count sweep, eager per-dispatch kernel times (the options below "
+                        "that switch parts off act on this form); without it only the main line is timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step of the main line returned "
+                        "(obs, reward, terminated, truncated, terminal_observation) as DIR/<name>.npy, float32")
     p.add_argument("--envs", type=int, default=ENVS_PER_GPU, help="envs per GPU")
     p.add_argument("--physics", default="PYB")
     p.add_argument("--precision", default="fp64", choices=["fp64", "fp32"],
@@ -87,7 +102,11 @@ def parse():
                    help="internal: run only config 5's world-1 RCCL step + all-gather record and print it "
                         "(the parent bench runs this as a child process)")
     p.add_argument("--gather-warmup", type=int, default=None, help="internal: --gather-leg warm-up steps")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        # the plain run: set up, warm up, time the K steps of the main line, print the line
+        args.no_configs = args.no_cpu_baseline = args.no_sweep = args.no_allgather = args.graph_only = True
+    return args
 
 
 # ----------------------------------------------------------------------------------------------
@@ -209,9 +228,11 @@ def capture_graph(graph):
     return torch.cuda.graph(graph, capture_error_mode="thread_local")
 
 
-def time_graph(stepper, acts, K, W, world, dev):
+def time_graph(stepper, acts, K, W, world, dev, keep_outputs=False):
     """W eager warm-up steps, then exactly K steps replayed from captured HIP graphs, bracketed by
-    barrier + synchronize; returns the max over ranks of the timed region (s) and the graph size."""
+    barrier + synchronize; returns the max over ranks of the timed region (s) and the graph size.
+    keep_outputs: time_graph.last_outputs = copies of what the last timed step returned (taken after
+    the timed region closed)."""
     nbuf = acts.shape[0]
     for k in range(W):
         stepper.step(acts[k % nbuf])
@@ -226,7 +247,7 @@ def time_graph(stepper, acts, K, W, world, dev):
     graph = torch.cuda.CUDAGraph()
     with capture_graph(graph):
         for k in range(G):
-            stepper.step(acts[k % nbuf])
+            ret = stepper.step(acts[k % nbuf])
     graph.replay()                                           # untimed: warms the graph
     torch.cuda.synchronize()
     if world > 1:
@@ -245,9 +266,36 @@ def time_graph(stepper, acts, K, W, world, dev):
     el = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    if keep_outputs:
+        # env.step returns views of persistent device buffers: after the last replay they hold the
+        # outputs of the last timed step
+        obs, rew, term, trunc, info = ret
+        time_graph.last_outputs = {"obs": obs.clone(), "reward": rew.clone(), "terminated": term.clone(),
+                                   "truncated": trunc.clone(),
+                                   "terminal_observation": info["terminal_observation"].clone()}
     del graph
     time_graph.last_event_ms = ev0.elapsed_time(ev1) / K     # device time per replayed step (this rank)
     return float(el.item()), G
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, outputs, rank, world):
+    """--dump-outputs: the last timed step's outputs as path/<name>.npy (float32; at N > 1 each rank
+    writes its shard as <name>.rank<r>.npy).  Above the budget: the same seeded sample of env rows
+    from every array, in ascending order (envs.npy names the rows)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.to(torch.float32).cpu().numpy() for k, v in outputs.items()}
+    E = next(iter(arrs.values())).shape[0]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = max(1, int(E * DUMP_BUDGET_BYTES / (total + 8 * E)))
+        rows = np.sort(np.random.default_rng(2024).choice(E, size=keep, replace=False))
+        arrs = {k: np.ascontiguousarray(a[rows]) for k, a in arrs.items()}
+        arrs["envs"] = rows.astype(np.float32 if E < 2 ** 24 else np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy" if world == 1 else f"{k}.rank{rank}.npy"), a)
 
 
 def kernel_times(env, acts, n, stepper=None):
@@ -498,7 +546,7 @@ def guarded(fn, *a, **kw):
 
 
 def bench_race(level, drones, physics, racemode, precision, E, K, W, world, rank, dev, seed,
-               sharded_gather=False, policy_spec=None, graph_only=False, global_envs=None):
+               sharded_gather=False, policy_spec=None, graph_only=False, global_envs=None, dump=None, lean=False):
     """one MultiRaceAviary workload; E envs per GPU, or global_envs in total (strong scaling)"""
     from gym_pybullet_adrp_amd import _lib
     make = race_make(level, drones, physics, racemode, precision, dev)
@@ -523,8 +571,10 @@ def bench_race(level, drones, physics, racemode, precision, E, K, W, world, rank
                 policy.act(env._obs, out=pact)
                 return env.step(pact)
         stepper = _Loop()
-    elapsed, G = time_graph(stepper, acts, K, W, world, dev)
+    elapsed, G = time_graph(stepper, acts, K, W, world, dev, keep_outputs=dump is not None)
     step_ms = time_graph.last_event_ms
+    if dump is not None:
+        dump_outputs(dump, time_graph.last_outputs, rank, world)
     # closed loop: the timed region holds the policy launch too, so the step kernel's own time comes
     # from its dispatch events on the actor-driven steps
     eager = None if graph_only else kernel_times(env, acts, min(K, 512), stepper)
@@ -540,7 +590,10 @@ def bench_race(level, drones, physics, racemode, precision, E, K, W, world, rank
            "envs_per_gpu": E, "global_envs": total, "kernel": env.kernel_name,
            "roofline": valu_roofline(env, step_ms, eager, key, precision),
            "timed_region": f"{K // G} replays of a {G}-step HIP graph"}
-    if policy is not None:
+    if policy is not None and lean:   # the plain run: no launches beside the timed steps
+        rec["workload"] += f"; closed loop: on-device PPO actor ({policy_spec}) each step"
+        policy.close()
+    elif policy is not None:
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
         for a, b in ev:
             a.record()
@@ -565,7 +618,7 @@ def bench_race(level, drones, physics, racemode, precision, E, K, W, world, rank
     return rec
 
 
-def bench_hover(args, precision, E, K, W, world, rank, dev, sweep=False, sharded_gather=False):
+def bench_hover(args, precision, E, K, W, world, rank, dev, sweep=False, sharded_gather=False, dump=None):
     from gym_pybullet_adrp_amd import _lib
     make = hover_make(precision, args.physics, dev)
     sharded = None
@@ -577,8 +630,10 @@ def bench_hover(args, precision, E, K, W, world, rank, dev, sweep=False, sharded
         env = make(num_envs=E, env_offset=0)
     env.reset()
     acts = hover_actions(E, dev, 1 + rank)
-    elapsed, G = time_graph(env, acts, K, W, world, dev)
+    elapsed, G = time_graph(env, acts, K, W, world, dev, keep_outputs=dump is not None)
     step_ms = time_graph.last_event_ms
+    if dump is not None:
+        dump_outputs(dump, time_graph.last_outputs, rank, world)
     eager = None if args.graph_only else kernel_times(env, acts, min(K, 512))
     rec = {"value": E * world * K / elapsed, "ms_per_step": elapsed / K * 1e3,
            "kernel": env.kernel_name,
@@ -764,7 +819,8 @@ def main():
     hover_cfg = None
     if args.task == "race":
         rec = bench_race(args.level, args.drones, args.physics, args.racemode, args.precision, E, K, W, world, rank,
-                         local, 2, sharded_gather=world > 1 and not args.no_allgather, policy_spec=args.policy)
+                         local, 2, sharded_gather=world > 1 and not args.no_allgather, policy_spec=args.policy,
+                         graph_only=not args.full, dump=args.dump_outputs, lean=not args.full)
         result.update({"value": rec.pop("value"), "ms_per_step": rec.pop("ms_per_step"),
                        "data": "synthetic: level preset resets (device Philox), FULLSTATE targets start + U(+-0.3) m"
                        if not args.policy else "synthetic: level preset resets; setpoints from the reference's PPO actor",
@@ -776,7 +832,7 @@ def main():
     else:
         rec, hover_cfg = bench_hover(args, args.precision, E, K, W, world, rank, local,
                                      sweep=world == 1 and not args.no_sweep,
-                                     sharded_gather=world > 1 and not args.no_allgather)
+                                     sharded_gather=world > 1 and not args.no_allgather, dump=args.dump_outputs)
         result.update({"value": rec.pop("value"), "ms_per_step": rec.pop("ms_per_step"),
                        "data": "synthetic: device-RNG airborne initial states around (0,0,1), U[-1,1] RPM actions",
                        "config": {"workload": f"HoverAviary Physics.{args.physics} 240/30 Hz (8 sub-steps), {E} envs "

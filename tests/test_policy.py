@@ -1,7 +1,10 @@
 """On-device policy path, CPU part: the oracle's RLController transforms against the
 reference's own outputs (tests/golden/policy_golden.npz), the oracle actor against a torch
 fp32 forward, and the SB3 zip loader.  The kernel itself: tests/test_policy_gpu.py."""
+import io
+import json
 import os
+import zipfile
 
 import numpy as np
 import pytest
@@ -43,11 +46,37 @@ def test_actor_matches_torch_fp32(name):
     assert p.min() >= -1 and p.max() <= 1
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/user_controller"), reason="reference zips not present")
+def _sb3_zip(path, name):
+    """a model zip in the layout SB3's save() writes and the reference's user_controller zips have:
+    `policy.pth` = torch.save of the policy's state dict (the stored actor weights of `name`, beside
+    critic and log_std entries that the actor loader has to pass over), `data` = the JSON of the
+    constructor arguments (policy_kwargs.activation_fn as the class's repr; absent for the default
+    Tanh policy, as in example_RL_model.zip)"""
+    from gym_pybullet_adrp_amd.policy import ACTOR_KEYS, CRITIC_KEYS
+    w, relu = weights(name)
+    sd = {k: torch.from_numpy(np.array(w[i])) for i, k in enumerate(ACTOR_KEYS)}
+    h = w[2].shape[0]
+    rng = np.random.default_rng(5)
+    for k, shape in zip(CRITIC_KEYS, ((w[0].shape[0], 49), (w[0].shape[0],), (h, w[0].shape[0]), (h,), (1, h), (1,), (4,))):
+        sd[k] = torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
+    buf = io.BytesIO()
+    torch.save(sd, buf)
+    data = {"policy_class": {":type:": "<class 'abc.ABCMeta'>", "__module__": "stable_baselines3.common.policies"},
+            "verbose": 0, "policy_kwargs": {}}
+    if relu:
+        data["policy_kwargs"] = {":type:": "<class 'dict'>", "net_arch": [{"pi": [h, h], "vf": [h, h]}],
+                                 "activation_fn": "<class 'torch.nn.modules.activation.ReLU'>"}
+    with zipfile.ZipFile(path, "w") as zf:
+        zf.writestr("data", json.dumps(data))
+        zf.writestr("policy.pth", buf.getvalue())
+        zf.writestr("_stable_baselines3_version", "2.3.2")
+    return path
+
+
 @pytest.mark.parametrize("name", ZIPS)
-def test_sb3_zip_loader(name):
+def test_sb3_zip_loader(name, tmp_path):
     from gym_pybullet_adrp_amd.policy import ACTOR_KEYS, load_sb3_zip
-    w, act = load_sb3_zip(f"/root/reference/user_controller/{name}.zip")
+    w, act = load_sb3_zip(_sb3_zip(str(tmp_path / f"{name}.zip"), name))
     for i, k in enumerate(ACTOR_KEYS):
         np.testing.assert_array_equal(w[k], G[f"{name}_w{i}"])
     assert act == ("relu" if name == "twogates" else "tanh")

@@ -5,7 +5,7 @@
 # gpurun_out/TAG/; commit the summaries you keep under profiles/.
 #
 #   tools/gpu.sh check TAG             the driver's bench form (K = 20) + the focused parity tests
-#   tools/gpu.sh evidence TAG          GPU suite, smoke, default bench line (K = 2000), driver form (K = 20)
+#   tools/gpu.sh evidence TAG          GPU suite, smoke, the full bench line (--full, K = 2000), driver form (plain, K = 20)
 #   tools/gpu.sh prof TAG              rocprofv3 kernel-trace stats of the graph-replayed launches per workload
 #   tools/gpu.sh pmc TAG [alg fp64 fp32]   PMC passes: HBM traffic + VALU counters (tools/pmc_summary.py folds them)
 #   tools/gpu.sh fold TAG              (CPU side, after the pmc run merged back) fold the passes into
@@ -21,7 +21,7 @@ CMD="$1"; TAG="${2:-run}"; shift 2
 O="$R/gpurun_out/$TAG"
 mkdir -p "$O"
 PROF="cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv"
-NB="python3 $R/bench.py --no-cpu-baseline --no-configs --graph-only"
+NB="python3 $R/bench.py --full --no-cpu-baseline --no-configs --graph-only"
 RACE3="--task race --level level0 --drones 2 --envs 2048 --physics PYB --racemode COMPARE --steps 1000 --warmup 50"
 RACE4="--task race --level level3 --drones 4 --envs 4096 --physics PYB_DW --racemode COMPETE --steps 1000 --warmup 50"
 
@@ -56,7 +56,7 @@ case "$CMD" in
   evidence)
     steps "pytest_gpu|900|python -u -m pytest tests -m gpu -x -q --timeout 150 --timeout-method thread" \
           "smoke|200|python -c 'import __graft_entry__ as g; g.smoke()'" \
-          "bench|420|python bench.py > $O/bench.json" \
+          "bench|420|python bench.py --full > $O/bench.json" \
           "bench_k20|420|python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_k20.json" ;;
   prof)
     steps "prof_c2_fp64|200|$PROF -d $O/prof_c2_fp64 -o k -- $NB --steps 2000" \
@@ -130,7 +130,7 @@ case "$CMD" in
         IFS=',' read -r -a parts <<< "$ARM"
         envs=("ADRP_LIB=${parts[0]}" "${parts[@]:1}")
         # shellcheck disable=SC2086
-        env "${envs[@]}" timeout -k 10 150 python bench.py --no-cpu-baseline --no-configs $BENCH_ARGS > "$O/ab_last.log" 2>&1 \
+        env "${envs[@]}" timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-configs $BENCH_ARGS > "$O/ab_last.log" 2>&1 \
           || { tail -5 "$O/ab_last.log"; exit 1; }
         python3 - "$ARM" "$O/ab_last.log" <<'PY'
 import json, sys

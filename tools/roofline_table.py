@@ -4,7 +4,7 @@ usage: python tools/roofline_table.py gpurun_out/TAG ROUND [BENCH_JSON ...]
        (e.g. gpurun_out/r6p r6 profiles/r6_bench.json profiles/r6_bench_k20.json)
 
 For every workload directory prof_<cfg>/ of the run (rocprofv3 --kernel-trace of `bench.py
---graph-only ...`, whose JSON line is in prof_<cfg>.log):
+--full --graph-only ...`, whose JSON line is in prof_<cfg>.log):
   - the step kernel's launches are split by grid size: the benched env count (the most frequent
     grid) and, for the hover line, the roofline sweep's larger grids (bench.py roofline_sweep);
     profiles/ROUND_rocprof_<cfg>_E<E>_kernel_stats.csv holds one row per (kernel, grid), so the
