@@ -585,16 +585,7 @@ __device__ __forceinline__ void clamp100_wv(V3<double>& w, V3<double>& v) {
     }
 }
 
-__device__ __forceinline__ void clamp100_wv(V3<float>& w, V3<float>& v, const ChainK<float>&) { clamp100_wv(w, v); }
-__device__ __forceinline__ void clamp100_wv(V3<double>& w, V3<double>& v, const ChainK<double>& k) {
-    const double c = k.c100;
-    const bool big = (__builtin_fabs(w.x) > c) | (__builtin_fabs(w.y) > c) | (__builtin_fabs(w.z) > c) |
-                     (__builtin_fabs(v.x) > c) | (__builtin_fabs(v.y) > c) | (__builtin_fabs(v.z) > c);
-    if (__builtin_expect(__any(big), 0)) {
-        w = {clamp100_sel(w.x), clamp100_sel(w.y), clamp100_sel(w.z)};
-        v = {clamp100_sel(v.x), clamp100_sel(v.y), clamp100_sel(v.z)};
-    }
-}
+// (the hover chain carries ω in the body frame: its form of this clamp is clamp100_body, hover_kernel.h)
 
 // rotation matrix of a unit quaternion (body->world)
 template <typename Real>

@@ -17,11 +17,26 @@
 //   n_body       = P × (Rᵀzs) + τz·(Rᵀzs) + [G × ẑ]          P = Σ f_i p_i, G = Σ g_i p_i
 //   ω̇_b          = I⁻¹(n_b − k(1+|ω_b|) I∘ω_b − ω_b × I ω_b),   a_w = F_w/m − k(1+|v|) v
 //   v, ω += dt(·) (clamped ±100);  x += dt v;  q ← normalize((ω̂ sin, cos) ⊗ q)
+// ω is carried in the BODY frame through the sub-steps (wb = Rᵀω; state, obs and Bullet's API keep
+// the world frame: one rotation in before the loop, one out after it).  The exp map rotates the pose
+// about ω' itself, R' = exp([ω' dt]) R, so R'ᵀω' = Rᵀω' and
+//   wb' = wb + dt I⁻¹(n_b − k(1+|wb|) I∘wb − wb × I wb)          exactly, no rotation either way
+//   q'  = normalize(q ⊗ (s·wb', c))                              s = sin(|wb'|dt/2)/|wb'|, c = cos
+//   R'ᵀ col2(R) = third row of rot(δ), δ = (s·wb', c)/|q₁|       the next sub-step's Rᵀzs (lag on)
+//               = (2(δxδz − δwδy), 2(δyδz + δwδx), 1 − 2(δx² + δy²))
+// so no sub-step multiplies by a rotation matrix.  Per physics mode (template, no runtime branch):
+//   PYB, PYB_DW            third columns only: zs (lagged, thrust), zc (current, contact test)
+//   PYB_GND, .._GND_DRAG_DW  additionally the third row of the current R (prop heights) and zc
+//   PYB_DRAG               whole R and lagged Rs for Rs (Rᵀ drag): carries both matrices
+//   DYN                    its own explicit model (dyn_substep)
+// The ±100 clamp is on WORLD coordinates of ω: none can exceed 100 unless |wb| does, so behind a
+// wave-uniform __any(|wb| > 100): w = R wb, clamp, wb = Rᵀ w, committed per lane only where the
+// lane's own |wb| > 100 (clamp100_body; batch invariance).
 //
 // Latency design (E = 4096 is 64 waves on 256 CUs: the kernel is one wave's critical
 // path): no divides or IEEE sqrt in the sub-step chain (reciprocal constants, 1-ulp
-// hardware rcp/sqrt/rsq), small-angle sin/cos polynomial, the lagged link basis is the
-// previous sub-step's rotation matrix (carried, not recomputed), the action-ring loads
+// hardware rcp/sqrt/rsq), small-angle sin/cos polynomial, the lagged thrust axis is the
+// previous sub-step's z axis (carried, not recomputed), the action-ring loads
 // are issued at entry independent of the ring head, rows are written with 16-byte
 // per-lane stores straight from registers (no LDS, no barrier).
 #pragma once
@@ -167,30 +182,88 @@ __device__ __forceinline__ float rpm_gain(float a) {
     return 1.0f + m;
 }
 
-// One Bullet stepSimulation of one drone after the reference's force calls.
-// R = rot(b.q) on entry; Rs = rotation of the cached link basis.  On exit R/Rs are the
-// matrices the next sub-step needs.  wn = |b.w| on entry and on exit (the exp map's |w| is the
-// next sub-step's |R^T w| of the damping term: a rotation keeps the norm, so the chain takes one
-// square root per sub-step, not two; rounding-level difference).  Returns true if the plane
-// contact model acted.
+// third column (body z axis in world) and third row of rot_fm(q): the same expressions, so the same bits
+template <typename Real>
+__device__ __forceinline__ V3<Real> col2_fm(Q4<Real> q) {
+    const Real x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
+    const Real xx = q.x * x2;
+    const Real wx = q.w * x2, wy = q.w * y2;
+    return {fmx(q.x, z2, wy), fmx(q.y, z2, -wx), Real(1) - fmx(q.y, y2, xx)};
+}
+template <typename Real>
+__device__ __forceinline__ V3<Real> row2_fm(Q4<Real> q) {
+    const Real x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
+    const Real xx = q.x * x2;
+    const Real wx = q.w * x2, wy = q.w * y2;
+    return {fmx(q.x, z2, -wy), fmx(q.y, z2, wx), Real(1) - fmx(q.y, y2, xx)};
+}
+
+// What the PYB sub-step chain carries from one sub-step to the next beside the Body.  ω lives in the
+// body frame inside the loop (header comment: no rotation of ω either way, no rotation matrix).
+template <typename Real>
+struct Chain {
+    V3<Real> wb;      // body-frame angular velocity R^T ω
+    Real wn;          // |wb| (= |ω|: the damping term's and the exp map's norm, one sqrt per sub-step)
+    V3<Real> zs;      // thrust axis: third column of the cached link basis (world)
+    V3<Real> zc;      // third column of the current pose's matrix (world)
+    V3<Real> m3;      // R^T zs
+    V3<Real> dti;     // dt I^-1
+    M3<Real> R, Rs;   // PYB_DRAG only (drag goes world -> body -> cached link basis): rot_fm(q), rot_fm(ql)
+};
+
+__device__ __forceinline__ float clamp100_(float x) { return __builtin_amdgcn_fmed3f(x, -100.0f, 100.0f); }
+__device__ __forceinline__ double clamp100_(double x) { return clamp100_sel(x); }
+
+// btClamp(x, -100, 100) of the six coordinate velocities (clamp100_wv) for the body-frame chain.
+// v as there.  ω's coordinates are WORLD coordinates; none can exceed 100 unless |wb| = |ω| does, so
+// behind a wave-uniform test of the norm: w = R wb, clamp, wb = R^T w, and the norm again, with R the
+// pre-update pose's matrix (what Bullet clamps against).  The result is committed per lane, only where
+// the lane's own |wb| > 100: a slow env never takes the round trip because a wave mate spins fast
+// (batch invariance).  NaN fails the test and passes through, as in btClamp.
+template <typename Real>
+__device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn, V3<Real>& v, const ChainK<Real>& K) {
+    const Real c = K.c100;
+    const bool fast = wn > c;
+    bool big = fast;
+    if constexpr (sizeof(Real) == 8) {   // (fp64 has no med3: the select form of v's clamp goes behind the test too)
+        const bool bx = fabs_(v.x) > c, by = fabs_(v.y) > c, bz = fabs_(v.z) > c;
+        big = fast | bx | by | bz;
+    } else {
+        v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
+    }
+    if (__builtin_expect(__any(big), 0)) {
+        if constexpr (sizeof(Real) == 8) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
+        const M3<Real> R = rot_fm(q);
+        const V3<Real> w = mul(R, wb);
+        const V3<Real> wc = mulT(R, v3(clamp100_(w.x), clamp100_(w.y), clamp100_(w.z)));
+        const Real wnc = hsqrt_nn_(dot(wc, wc), K);
+        wb = v3(fast ? wc.x : wb.x, fast ? wc.y : wb.y, fast ? wc.z : wb.z);
+        wn = fast ? wnc : wn;
+    }
+}
+
+// One Bullet stepSimulation of one drone after the reference's force calls, ω in the body frame
+// (st.wb; b.w is not touched: the caller rotates st.wb back once after the last sub-step).  On entry
+// st holds the thrust axis, the current z axis, R^T zs and |wb| of the pose b.q; on exit those of the
+// new pose.  Returns true if the plane contact model acted.
 // K: the chain's literal constants (pinned into VGPRs by the fp64 caller, ChainK)
 template <typename Real, int PH>
-__device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, M3<Real>& R, M3<Real>& Rs,
-                                            const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z, Real& wn,
+__device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
+                                            const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
                                             const ChainK<Real>& K) {
     constexpr bool GND = (PH == ADRP_PHYS_PYB_GND || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
+    constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
     // _physics: 4 prop forces + z torque on link 4, LINK_FRAME, cached basis
-    const V3<Real> zs = col2(Rs);
+    const V3<Real> zs = st.zs;
     V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
-    const V3<Real> m3 = mulT(R, zs);
+    const V3<Real> m3 = st.m3;
     // P x m3 + tau_z m3
     V3<Real> nb = v3(fmx(tau_z, m3.x, fmx(P.y, m3.z, -(P.z * m3.y))), fmx(tau_z, m3.y, fmx(P.z, m3.x, -(P.x * m3.z))),
                      fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))));
-    bool cur_basis = false;
     if constexpr (GND) {
-        // getLinkStates(computeForwardKinematics=1) refreshes the cached basis first
-        cur_basis = true;
+        // getLinkStates(computeForwardKinematics=1) refreshes the cached basis first (so the drag
+        // below is applied in the current basis)
         const Real sqx = b.q.x * b.q.x, sqy = b.q.y * b.q.y, sqz = b.q.z * b.q.z, squ = b.q.w * b.q.w;
         const Real sarg = Real(-2) * (b.q.x * b.q.z - b.q.w * b.q.y);
         const Real den = squ - sqx - sqy + sqz, num = Real(2) * (b.q.y * b.q.z + b.q.w * b.q.x);
@@ -199,16 +272,17 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
         if (gate) {
             Real sg = 0;
             V3<Real> G = v3(Real(0), Real(0), Real(0));
+            const V3<Real> r2 = row2_fm(b.q);   // prop heights: the third row of the current pose's matrix
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                Real h = b.pos.z + R.a20 * a.px[i] + R.a21 * a.py[i] + R.a22 * a.pz[i];
+                Real h = b.pos.z + r2.x * a.px[i] + r2.y * a.py[i] + r2.z * a.pz[i];
                 h = h < a.gnd_clip ? a.gnd_clip : h;
                 const Real k = a.prop_r4 * rcp_(h);
                 const Real g = a.gnd_kf * rpm[i] * rpm[i] * k * k;
                 sg += g;
                 G = G + v3(g * a.px[i], g * a.py[i], g * a.pz[i]);
             }
-            Fw = Fw + sg * col2(R);
+            Fw = Fw + sg * st.zc;
             nb = nb + v3(G.y, -G.x, Real(0));
         }
     }
@@ -218,55 +292,74 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
         for (int i = 0; i < 4; ++i) s += b.prev_rpm[i];
         s = s * Real(0.10471975511965977);  // sum(2*pi*rpm/60)
         const V3<Real> dw = v3(-a.drag[0] * s * b.vel.x, -a.drag[1] * s * b.vel.y, -a.drag[2] * s * b.vel.z);
-        const V3<Real> dl = mulT(R, dw);    // np.dot(base_rot.T, drag_factors * vel)
-        Fw = Fw + (cur_basis ? dw : mul(Rs, dl));
+        // np.dot(base_rot.T, drag_factors * vel), applied in the cached link basis
+        if constexpr (GND) Fw = Fw + dw;
+        else Fw = Fw + mul(st.Rs, mulT(st.R, dw));
     }
     // ---- Bullet: forwardKinematics, ABA of the floating base, semi-implicit Euler ----
-    const V3<Real> wb = mulT(R, b.w);
+    V3<Real> wb = st.wb;
     const V3<Real> Iw = v3(a.ixx * wb.x, a.iyy * wb.y, a.izz * wb.z);
-    const Real kw = K.k004 + K.k004 * wn;
+    const Real kw = K.k004 + K.k004 * st.wn;
     // nb - kw Iw - wb x Iw
     const V3<Real> rhs = v3(fmx(wb.z, Iw.y, fmx(-wb.y, Iw.z, fmx(-kw, Iw.x, nb.x))),
                             fmx(wb.x, Iw.z, fmx(-wb.z, Iw.x, fmx(-kw, Iw.y, nb.y))),
                             fmx(wb.y, Iw.x, fmx(-wb.x, Iw.y, fmx(-kw, Iw.z, nb.z))));
-    const V3<Real> wdot = mul(R, v3(rhs.x * a.inv_ixx, rhs.y * a.inv_iyy, rhs.z * a.inv_izz));
     const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(b.vel, b.vel), K);
     const V3<Real> acc = v3(fmx(-kv, b.vel.x, a.inv_mass * Fw.x), fmx(-kv, b.vel.y, a.inv_mass * Fw.y),
                             fmx(-kv, b.vel.z, a.inv_mass * Fw.z));
-    b.w = v3(b.w.x + a.dt * wdot.x, b.w.y + a.dt * wdot.y, b.w.z + a.dt * wdot.z);
+    // ω' = ω + dt R I^-1 rhs in the body frame of the pose the exp map is about to leave: the map
+    // rotates about ω' itself, so R'^T ω' = R^T ω' and the body-frame update needs no rotation
+    wb = v3(fmx(st.dti.x, rhs.x, wb.x), fmx(st.dti.y, rhs.y, wb.y), fmx(st.dti.z, rhs.z, wb.z));
     b.vel = v3(b.vel.x + a.dt * acc.x, b.vel.y + a.dt * acc.y, b.vel.z + a.dt * acc.z);
-    clamp100_wv(b.w, b.vel, K);
+    Real ang = hsqrt_nn_(dot(wb, wb), K);
+    clamp100_body(b.q, wb, ang, b.vel, K);
+    st.wb = wb;
+    st.wn = ang;
     b.pos = v3(fmx(a.dt, b.vel.x, b.pos.x), fmx(a.dt, b.vel.y, b.pos.y), fmx(a.dt, b.vel.z, b.pos.z));
     // exp-map quaternion update (btMultiBody::stepPositionsMultiDof)
-    Real ang = hsqrt_nn_(dot(b.w, b.w), K);
-    wn = ang;
     if (ang > a.ang_max) ang = a.ang_max;          // |w| dt > ANGULAR_MOTION_THRESHOLD
     // sin(|w| dt / 2) / |w| = (dt / 2) sinc(|w| dt / 2): no reciprocal, and Bullet's small-angle
     // form (|w| < 0.001: 0.5 dt - dt^3 |w|^2 / 48) is the same series to rounding
     Real sinc, ch;
     expmap_sinc_cos(Real(0.5) * ang * a.dt, &sinc, &ch, K);
     const Real sc = (Real(0.5) * a.dt) * sinc;
-    const V3<Real> ax = sc * b.w;
+    const V3<Real> ax = sc * wb;
+    // (R ax, ch) (x) q0 = q0 (x) (ax, ch): the world-frame increment on the left is the body-frame one on the right
     const Q4<Real> q0 = b.q;
-    const Q4<Real> q1 = {ch * q0.x + ax.x * q0.w + ax.y * q0.z - ax.z * q0.y,
-                         ch * q0.y + ax.y * q0.w + ax.z * q0.x - ax.x * q0.z,
-                         ch * q0.z + ax.z * q0.w + ax.x * q0.y - ax.y * q0.x,
+    const Q4<Real> q1 = {ch * q0.x + ax.x * q0.w + ax.z * q0.y - ax.y * q0.z,
+                         ch * q0.y + ax.y * q0.w + ax.x * q0.z - ax.z * q0.x,
+                         ch * q0.z + ax.z * q0.w + ax.y * q0.x - ax.x * q0.y,
                          ch * q0.w - ax.x * q0.x - ax.y * q0.y - ax.z * q0.z};
     const Real inv = quat_inv_norm(q1.x * q1.x + q1.y * q1.y + q1.z * q1.z + q1.w * q1.w, K);
     // the basis cached by this step's forwardKinematics is the pre-integration pose
     if (a.link_lag) {
-        b.ql = b.q;
-        Rs = R;
+        b.ql = q0;
+        st.zs = st.zc;
+        // R'^T col2(R) = third row of the rotation of the increment d = (ax, ch) / |q1|
+        const Real s2 = (inv + inv) * inv;
+        st.m3 = v3(s2 * (ax.x * ax.z - ch * ax.y), s2 * (ax.y * ax.z + ch * ax.x),
+                   Real(1) - s2 * (ax.x * ax.x + ax.y * ax.y));
+        if constexpr (FULL) st.Rs = st.R;
     }
     b.q = {q1.x * inv, q1.y * inv, q1.z * inv, q1.w * inv};
-    R = rot_fm(b.q);
-    if (!a.link_lag) Rs = R;
+    if constexpr (FULL) {
+        st.R = rot_fm(b.q);
+        st.zc = col2(st.R);
+    } else {
+        st.zc = col2_fm(b.q);
+    }
+    if (!a.link_lag) {
+        st.zs = st.zc;
+        st.m3 = v3(Real(0), Real(0), Real(1));
+        if constexpr (FULL) st.Rs = st.R;
+    }
     // plane contact model: non-penetration, no inward velocity.
     // lowest point of the body cylinder: cos(tilt) = R22, sin(tilt) = |(R02, R12)|.  It is at
     // least z + zoff - hh - r below the centre, so a wave whose drones are all higher than that
     // skips the exact test (same result)
     if (__builtin_expect(__any(b.pos.z + a.coll_zoff <= a.coll_hh + a.coll_r + Real(1e-6)), 0)) {
-        const Real low = b.pos.z + a.coll_zoff - a.coll_hh * fabs_(R.a22) - a.coll_r * hsqrt_nn_(R.a02 * R.a02 + R.a12 * R.a12);
+        const Real low = b.pos.z + a.coll_zoff - a.coll_hh * fabs_(st.zc.z) -
+                         a.coll_r * hsqrt_nn_(st.zc.x * st.zc.x + st.zc.y * st.zc.y);
         if (low < Real(0)) {
             b.pos.z -= low;
             if (b.vel.z < Real(0)) b.vel.z = Real(0);
@@ -823,8 +916,6 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             t2 += (i & 1) ? -r2 : r2;
         }
         const Real tau_z = t2 * C.km;    // KM*(rpm0^2 - rpm1^2 + rpm2^2 - rpm3^2), IROS sign
-        M3<Real> R = rot_fm(b.q);
-        M3<Real> Rs = lag ? rot_fm(b.ql) : R;
         // the chain's constants in VGPRs for the whole loop (fp64: no 64-bit literal operands)
         ChainK<Real> K = chain_consts<Real>();
         HoverConst<Real> Cp = C;
@@ -834,9 +925,25 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             pin(Cp.ixx); pin(Cp.iyy); pin(Cp.izz); pin(Cp.inv_ixx); pin(Cp.inv_iyy); pin(Cp.inv_izz);
             pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
         }
-        Real wn = hsqrt_nn_(dot(b.w, b.w), K);
+        // into the body frame: ω, the thrust axis (third column of the cached link basis) and its
+        // body coordinates; the loop carries these, not the matrices
+        Chain<Real> st{};
+        {
+            const M3<Real> R = rot_fm(b.q);
+            const M3<Real> Rs = lag ? rot_fm(b.ql) : R;
+            st.wb = mulT(R, b.w);
+            st.zc = col2(R);
+            st.zs = col2(Rs);
+            st.m3 = lag ? mulT(R, st.zs) : v3(Real(0), Real(0), Real(1));
+            if constexpr (DRAG) {
+                st.R = R;
+                st.Rs = Rs;
+            }
+        }
+        st.wn = hsqrt_nn_(dot(b.w, b.w), K);
+        st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
         auto substep = [&]() {
-            touched |= pyb_substep<Real, PH>(Cp, b, R, Rs, rpm, sum_f, P, tau_z, wn, K);
+            touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K);
 #pragma unroll
             for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
         };
@@ -846,6 +953,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         } else {
             for (int s = 0; s < C.S; ++s) substep();
         }
+        b.w = mul(rot_fm(b.q), st.wb);   // state, obs and the stored link_quat stay in the world frame
     }
     RACE_MARK(t2);
     if (touched && a.contact_count && (!split || threadIdx.x == 0)) atomicAdd(a.contact_count, 1);
