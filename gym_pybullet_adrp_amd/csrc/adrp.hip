@@ -35,7 +35,7 @@ extern "C" const char* adrp_last_error(const adrp_t* h) { return h ? h->err.c_st
 // defaults (reference constructors; cf2x_IROS.urdf constants; level0.yaml track)
 // ---------------------------------------------------------------------------------------------
 extern "C" int adrp_default_config(int task, adrp_config* c) {
-    if (!c || (task != ADRP_TASK_HOVER && task != ADRP_TASK_RACE)) return seterr(nullptr, ADRP_ERR_INVALID, "task");
+    if (!c || (task != ADRP_TASK_HOVER && task != ADRP_TASK_RACE && task != ADRP_TASK_MULTIHOVER)) return seterr(nullptr, ADRP_ERR_INVALID, "task");
     memset(c, 0, sizeof *c);
     c->struct_size = sizeof(adrp_config);
     c->task = task;
@@ -54,7 +54,7 @@ extern "C" int adrp_default_config(int task, adrp_config* c) {
     d.dw_coeff[0] = 2267.18; d.dw_coeff[1] = 0.16; d.dw_coeff[2] = -0.11;
     const double pp[4][2] = {{0.028, 0.028}, {-0.028, 0.028}, {-0.028, -0.028}, {0.028, -0.028}};
     for (int i = 0; i < 4; ++i) { d.prop_pos[i][0] = pp[i][0]; d.prop_pos[i][1] = pp[i][1]; }
-    if (task == ADRP_TASK_HOVER) {
+    if (task == ADRP_TASK_HOVER || task == ADRP_TASK_MULTIHOVER) {
         c->act_type = ADRP_ACT_RPM;
         c->num_drones = 1;
         c->pyb_freq = 240; c->ctrl_freq = 30;                // HoverAviary.py:18-19
@@ -62,6 +62,13 @@ extern "C" int adrp_default_config(int task, adrp_config* c) {
         c->init_xyz[0][2] = d.collision_h / 2 - d.collision_z_offset + 0.1;  // BaseAviary.py:195-197
         c->target_pos[2] = 1.0;
         c->episode_len_sec = 8.0;
+        if (task == ADRP_TASK_MULTIHOVER) {                  // MultiHoverAviary.py:17 num_drones = 2
+            c->num_drones = 2;
+            for (int n = 0; n < c->num_drones; ++n) {        // BaseAviary.py:194-197
+                c->init_xyz[n][0] = 4 * d.l * n; c->init_xyz[n][1] = 4 * d.l * n;
+                c->init_xyz[n][2] = d.collision_h / 2 - d.collision_z_offset + 0.1;
+            }
+        }
     } else {
         c->act_type = ADRP_ACT_FULLSTATE;
         c->num_drones = 2;
@@ -182,6 +189,33 @@ static int upload_const(adrp_t* h) {
         return ADRP_ERR_DEVICE;
     h->cf2x = is_cf2x<Real>(h->cfg);
     if (const char* env = getenv("ADRP_HOVER_GENERIC")) h->cf2x = h->cf2x && atoi(env) == 0;   // A/B: runtime constants
+    return ADRP_OK;
+}
+
+// MultiHoverAviary: [HoverConst | HoverReset | MultiConst] (multihover_const)
+template <typename Real>
+static int upload_multihover_const(adrp_t* h) {
+    const adrp_config& c = h->cfg;
+    const HoverConst<Real> k = hover_const<Real>(c);
+    const HoverReset<Real> r = hover_reset_dist<Real>(c);
+    MultiConst<Real> m;
+    memset(&m, 0, sizeof m);
+    m.N = c.num_drones;
+    m.dw1 = Real(c.drone.dw_coeff[0]); m.dw2 = Real(c.drone.dw_coeff[1]); m.dw3 = Real(c.drone.dw_coeff[2]);
+    m.prop_r = Real(c.drone.prop_radius);
+    for (int n = 0; n < c.num_drones; ++n)
+        for (int j = 0; j < 3; ++j) {
+            m.init_xyz[n][j] = Real(c.init_xyz[n][j]);
+            m.init_rpy[n][j] = Real(c.init_rpy[n][j]);
+            // TARGET_POS = INIT_XYZS + [0, 0, 1/(i+1)] in float64 (MultiHoverAviary.py:71)
+            m.target[n][j] = Real(c.init_xyz[n][j] + (j == 2 ? 1.0 / (n + 1) : 0.0));
+        }
+    const size_t off = multihover_const_offset<Real>();
+    if (hipMalloc(&h->cblk, off + sizeof m) != hipSuccess) return ADRP_ERR_OOM;
+    if (hipMemcpy(h->cblk, &k, sizeof k, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((char*)h->cblk + sizeof k, &r, sizeof r, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy((char*)h->cblk + off, &m, sizeof m, hipMemcpyHostToDevice) != hipSuccess)
+        return ADRP_ERR_DEVICE;
     return ADRP_OK;
 }
 
@@ -322,6 +356,11 @@ extern "C" const char* adrp_kernel_name(const adrp_config* cfg) {
         return buf;
     }
     const int A = hover_act_dim(cfg->act_type);
+    if (cfg->task == ADRP_TASK_MULTIHOVER) {
+        snprintf(buf, sizeof buf, "multihover_step<%s,%s,A%d,G%d>", cfg->precision ? "f64" : "f32", ph[p], A,
+                 mh_group(cfg->num_drones));
+        return buf;
+    }
     if (hover_has_pid(cfg->act_type)) {
         static const char* ctl[] = {"", "", "", "PID", "VEL", "ONE_D_PID"};
         snprintf(buf, sizeof buf, "hover_step<%s,%s,A%d,Bn,generic,%s>", cfg->precision ? "f64" : "f32", ph[p], A,
@@ -373,6 +412,16 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
             return seterr(nullptr, ADRP_ERR_INVALID, "HoverAviary act_type must be RPM, ONE_D_RPM, PID, VEL or ONE_D_PID");
         if (c.action_buffer_size <= 0 || c.action_buffer_size > 4096)
             return seterr(nullptr, ADRP_ERR_INVALID, "action_buffer_size");
+    } else if (c.task == ADRP_TASK_MULTIHOVER) {
+        if (c.num_drones < 1 || c.num_drones > ADRP_MAX_DRONES)
+            return seterr(nullptr, ADRP_ERR_INVALID, "MultiHoverAviary num_drones must be 1..8");
+        if (hover_has_pid(c.act_type))
+            return seterr(nullptr, ADRP_ERR_INVALID, "MultiHoverAviary act_type PID, VEL and ONE_D_PID are not supported "
+                                                     "(RPM or ONE_D_RPM)");
+        if (c.act_type != ADRP_ACT_RPM && c.act_type != ADRP_ACT_ONE_D_RPM)
+            return seterr(nullptr, ADRP_ERR_INVALID, "MultiHoverAviary act_type must be RPM or ONE_D_RPM");
+        if (c.action_buffer_size <= 0 || c.action_buffer_size > 4096)
+            return seterr(nullptr, ADRP_ERR_INVALID, "action_buffer_size");
     } else if (c.task == ADRP_TASK_RACE) {
         if (c.num_drones < 1 || c.num_drones > ADRP_MAX_DRONES)
             return seterr(nullptr, ADRP_ERR_INVALID, "MultiRaceAviary num_drones must be 1..8");
@@ -411,7 +460,7 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
         return rc;
     };
     DeviceGuard g(device);
-    const size_t ring_bytes = size_t(h->B) * h->A * h->E * sizeof(float);
+    const size_t ring_bytes = size_t(h->B) * h->A * EN * sizeof(float);   // [B][E*N][A] (race: none)
     if (hipMalloc(&h->f, h->nf_base * EN * h->real_size) != hipSuccess ||
         (ring_bytes && hipMalloc((void**)&h->ring, ring_bytes) != hipSuccess) ||
         hipMalloc((void**)&h->ist, h->ni * EN * sizeof(int32_t)) != hipSuccess ||
@@ -429,6 +478,8 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
     if (const char* env = getenv("ADRP_RACE_REFINE")) h->race_refine = atoi(env) != 0;
     if (const char* env = getenv("ADRP_RACE_PREDRAW")) h->race_predraw = atoi(env) != 0;
     const int rc = race ? (h->real_size == 8 ? upload_race_const<double>(h) : upload_race_const<float>(h))
+                   : c.task == ADRP_TASK_MULTIHOVER
+                        ? (h->real_size == 8 ? upload_multihover_const<double>(h) : upload_multihover_const<float>(h))
                         : (h->real_size == 8 ? upload_const<double>(h) : upload_const<float>(h));
     if (rc != ADRP_OK) return cleanup(seterr(h, rc, "constant block upload failed"));
     if (const char* env = getenv("ADRP_RESET_IMAGES")) h->img_period = atoi(env);
@@ -518,6 +569,9 @@ extern "C" int adrp_reset(adrp_t* h, const uint8_t* env_mask_dev, float* obs_dev
         return h->real_size == 8 ? race_reset<double>(h, env_mask_dev, obs_dev, s)
                                  : race_reset<float>(h, env_mask_dev, obs_dev, s);
     }
+    if (h->cfg.task == ADRP_TASK_MULTIHOVER)
+        return h->real_size == 8 ? multihover_reset<double>(h, env_mask_dev, obs_dev, s)
+                                 : multihover_reset<float>(h, env_mask_dev, obs_dev, s);
     return h->real_size == 8 ? hover_reset<double>(h, env_mask_dev, obs_dev, s)
                              : hover_reset<float>(h, env_mask_dev, obs_dev, s);
 }
@@ -532,6 +586,9 @@ extern "C" int adrp_step(adrp_t* h, const float* act_dev, float* obs_dev, float*
     if (h->cfg.task == ADRP_TASK_RACE)
         return h->real_size == 8 ? race_step<double>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s)
                                  : race_step<float>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s);
+    if (h->cfg.task == ADRP_TASK_MULTIHOVER)
+        return h->real_size == 8 ? multihover_step<double>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s)
+                                 : multihover_step<float>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s);
     return h->real_size == 8 ? hover_step<double>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s)
                              : hover_step<float>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s);
 }
@@ -666,6 +723,15 @@ __global__ void ring_set_kernel(float* __restrict__ ring, const void* src, int i
         }
 }
 
+// MultiHoverAviary: the per-env ints are replicated on the env's N columns from drone 0's
+__global__ void spread_ints_kernel(int32_t* __restrict__ ist, int ni, int E, int N) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const size_t EN = size_t(E) * N, c0 = size_t(e) * N;
+    for (int k = 0; k < ni; ++k)
+        for (int n = 1; n < N; ++n) ist[k * EN + c0 + n] = ist[k * EN + c0];
+}
+
 }  // namespace adrp
 
 // ---------------------------------------------------------------------------------------------
@@ -732,8 +798,9 @@ extern "C" int adrp_get_state(adrp_t* h, void* f_dev, int32_t* i_dev, void* stre
     const size_t EN = size_t(h->E) * h->N, nb = h->nf_base * EN, nr = size_t(h->B) * h->A * h->E;
     HIPCHK(h, hipMemcpyAsync(f_dev, h->f, nb * h->real_size, hipMemcpyDeviceToDevice, s));
     void* ring_dst = (char*)f_dev + nb * h->real_size;
-    if (h->B > 0) hipLaunchKernelGGL(ring_get_kernel, dim3((h->E + 255) / 256), dim3(256), 0, s, h->ring, ring_dst,
-                       int(h->real_size == 8), h->B, h->A, h->E);
+    // (the ring has one column per drone: E*N of them for MultiHoverAviary, N = 1 for HoverAviary)
+    if (h->B > 0) hipLaunchKernelGGL(ring_get_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, s, h->ring, ring_dst,
+                       int(h->real_size == 8), h->B, h->A, int(EN));
     HIPCHK(h, hipGetLastError());
     (void)nr;
     HIPCHK(h, hipMemcpyAsync(i_dev, h->ist, h->ni * EN * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -748,11 +815,15 @@ extern "C" int adrp_set_state(adrp_t* h, const void* f_dev, const int32_t* i_dev
     const size_t EN = size_t(h->E) * h->N, nb = h->nf_base * EN, nr = size_t(h->B) * h->A * h->E;
     HIPCHK(h, hipMemcpyAsync(h->f, f_dev, nb * h->real_size, hipMemcpyDeviceToDevice, s));
     const void* ring_src = (const char*)f_dev + nb * h->real_size;
-    if (h->B > 0) hipLaunchKernelGGL(ring_set_kernel, dim3((h->E + 255) / 256), dim3(256), 0, s, h->ring, ring_src,
-                       int(h->real_size == 8), h->B, h->A, h->E);
+    if (h->B > 0) hipLaunchKernelGGL(ring_set_kernel, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, s, h->ring, ring_src,
+                       int(h->real_size == 8), h->B, h->A, int(EN));
     HIPCHK(h, hipGetLastError());
     (void)nr;
     HIPCHK(h, hipMemcpyAsync(h->ist, i_dev, h->ni * EN * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (h->cfg.task == ADRP_TASK_MULTIHOVER && h->N > 1) {   // the env's ints are drone 0's
+        hipLaunchKernelGGL(spread_ints_kernel, dim3((h->E + 255) / 256), dim3(256), 0, s, h->ist, h->ni, h->E, h->N);
+        HIPCHK(h, hipGetLastError());
+    }
     return ADRP_OK;
 }
 
@@ -782,6 +853,8 @@ extern "C" int64_t adrp_step_bytes(const adrp_t* h) {
                             + int64_t(h->B - 1) * h->A * 4        // ring read
                             + int64_t(h->D) * 4                   // obs write
                             + 4 + 2;                              // reward, terminated, truncated
+    if (h->cfg.task == ADRP_TASK_MULTIHOVER)   // per drone; reward and flags per env; the ring is read from HBM whole
+        return ((per_env - 6 + int64_t(h->A) * 4) * h->N + 6) * h->E;
     return per_env * h->E;
 }
 

@@ -13,6 +13,7 @@
 
 #include "../../include/adrp.h"
 #include "hover_kernel.h"
+#include "multihover_kernel.h"
 #include "race_kernel.h"
 #include "race_quad.h"
 #include "device_guard.h"
@@ -28,7 +29,7 @@ struct adrp_handle {
     int nf_base = 0, ni = 0;
     size_t real_size = 4;
     void* f = nullptr;        // Real [nf_base][E*N]
-    float* ring = nullptr;    // [B*A][E]
+    float* ring = nullptr;    // [B][E*N][A] (hover tasks)
     int32_t* ist = nullptr;   // [ni][E*N]
     int32_t* counters = nullptr;  // device diagnostics (ground-model hits)
     void* cblk = nullptr;         // device HoverConst<Real> + HoverReset<Real>
@@ -120,6 +121,16 @@ inline HoverArgs<Real> hover_args(const adrp_t* h) {
     return a;
 }
 
+// MultiHoverAviary's constant block: [HoverConst | HoverReset | MultiConst]
+template <typename Real>
+constexpr size_t multihover_const_offset() {
+    return (sizeof(HoverConst<Real>) + sizeof(HoverReset<Real>) + 15) & ~size_t(15);
+}
+template <typename Real>
+inline const MultiConst<Real>* multihover_const(const adrp_t* h) {
+    return (const MultiConst<Real>*)((const char*)h->cblk + multihover_const_offset<Real>());
+}
+
 template <typename Real>
 constexpr size_t race_ticks_offset() { return (sizeof(RaceConst<Real>) + 255) & ~size_t(255); }
 
@@ -155,6 +166,11 @@ int hover_step(adrp_t* h, const float* act, float* obs, float* rew, uint8_t* ter
                hipStream_t s);
 template <typename Real>
 int hover_reset(adrp_t* h, const uint8_t* mask, float* obs, hipStream_t s);
+template <typename Real>
+int multihover_step(adrp_t* h, const float* act, float* obs, float* rew, uint8_t* term, uint8_t* trunc, float* tobs,
+                    hipStream_t s);
+template <typename Real>
+int multihover_reset(adrp_t* h, const uint8_t* mask, float* obs, hipStream_t s);
 template <typename Real>
 int hover_persist_launch(adrp_t* h, const HoverArgs<Real>& a, void* ctl, hipStream_t s);
 template <typename Real>

@@ -247,10 +247,12 @@ __device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn
 // st holds the thrust axis, the current z axis, R^T zs and |wb| of the pose b.q; on exit those of the
 // new pose.  Returns true if the plane contact model acted.
 // K: the chain's literal constants (pinned into VGPRs by the fp64 caller, ChainK)
-template <typename Real, int PH>
+// EXT: Fext, one more world-frame force through the centre of mass (MultiHoverAviary's downwash), is
+// added to the force sum; without it (HoverAviary) the argument is not read
+template <typename Real, int PH, bool EXT = false>
 __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
                                             const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
-                                            const ChainK<Real>& K) {
+                                            const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}) {
     constexpr bool GND = (PH == ADRP_PHYS_PYB_GND || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
@@ -296,6 +298,7 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
         if constexpr (GND) Fw = Fw + dw;
         else Fw = Fw + mul(st.Rs, mulT(st.R, dw));
     }
+    if constexpr (EXT) Fw = Fw + Fext;
     // ---- Bullet: forwardKinematics, ABA of the floating base, semi-implicit Euler ----
     V3<Real> wb = st.wb;
     const V3<Real> Iw = v3(a.ixx * wb.x, a.iyy * wb.y, a.izz * wb.z);
@@ -409,14 +412,13 @@ __device__ __forceinline__ void dyn_substep(const HoverConst<Real>& a, Body<Real
 }
 
 // BaseAviary.reset -> _housekeeping (+ the optional init_noise extension), Real precision
+// (a: the reset distribution; gid, tag: the Philox stream of the drone being reset)
 template <typename Real>
-__device__ __forceinline__ void hover_reset_state(const HoverArgs<Real>& args, const HoverConst<Real>& C, int e,
-                                                  Body<Real>& b, int32_t& sc, int32_t& ep) {
-    const HoverReset<Real>& a = *args.r;
-    const uint64_t gid = uint64_t(args.env_offset + e);
-    const U4 r0 = draw(args.seed, gid, uint32_t(ep), TAG_HOVER_RESET, 0);
-    const U4 r1 = draw(args.seed, gid, uint32_t(ep), TAG_HOVER_RESET, 1);
-    const U4 r2 = draw(args.seed, gid, uint32_t(ep), TAG_HOVER_RESET, 2);
+__device__ __forceinline__ void hover_reset_draw(const HoverReset<Real>& a, uint64_t seed, uint64_t gid, uint32_t tag,
+                                                 const HoverConst<Real>& C, Body<Real>& b, int32_t& sc, int32_t& ep) {
+    const U4 r0 = draw(seed, gid, uint32_t(ep), tag, 0);
+    const U4 r1 = draw(seed, gid, uint32_t(ep), tag, 1);
+    const U4 r2 = draw(seed, gid, uint32_t(ep), tag, 2);
     const uint32_t w0[4] = {r0.a, r0.b, r0.c, r0.d}, w1[4] = {r1.a, r1.b, r1.c, r1.d},
                    w2[4] = {r2.a, r2.b, r2.c, r2.d};
     Real p[3], e_[3], v[3], om[3];
@@ -444,6 +446,11 @@ __device__ __forceinline__ void hover_reset_state(const HoverArgs<Real>& args, c
     for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
     sc = 0;
     ep += 1;
+}
+template <typename Real>
+__device__ __forceinline__ void hover_reset_state(const HoverArgs<Real>& args, const HoverConst<Real>& C, int e,
+                                                  Body<Real>& b, int32_t& sc, int32_t& ep) {
+    hover_reset_draw(*args.r, args.seed, uint64_t(args.env_offset + e), TAG_HOVER_RESET, C, b, sc, ep);
 }
 
 // euler_xyz_fast_u's angles one at a time: the same expressions (the same contraction, so the same
@@ -707,6 +714,73 @@ __device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, cons
     }
 }
 
+// The PYB sub-step chain of one env.step of one drone: the prop force sums of the step's RPMs, ω and the
+// thrust axis into the body frame, S sub-steps (SC > 0: compile-time count, unrolled), ω back to the
+// world frame.  ext(b, st), unless NoExtForce, gives each sub-step one more world-frame force from the
+// state at its start (every lane of the wave calls it: it may exchange across lanes).  Returns true if
+// the plane contact model acted.
+struct NoExtForce {};
+template <typename Real, int PH, int SC, bool DRAG, typename Ext>
+__device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>& b, const Real rpm_in[4], bool lag,
+                                          Ext ext) {
+    constexpr bool EXT = !__is_same(Ext, NoExtForce);
+    // (a local copy: nothing the sub-steps store can alias it, so what depends on the RPMs alone is
+    // computed once for the unrolled sub-steps)
+    const Real rpm[4] = {rpm_in[0], rpm_in[1], rpm_in[2], rpm_in[3]};
+    Real sum_f = 0, t2 = 0;
+    V3<Real> P = v3(Real(0), Real(0), Real(0));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const Real r2 = rpm[i] * rpm[i];
+        const Real f = r2 * C.kf;
+        sum_f += f;
+        P = P + v3(f * C.px[i], f * C.py[i], f * C.pz[i]);
+        t2 += (i & 1) ? -r2 : r2;
+    }
+    const Real tau_z = t2 * C.km;    // KM*(rpm0^2 - rpm1^2 + rpm2^2 - rpm3^2), IROS sign
+    // the chain's constants in VGPRs for the whole loop (fp64: no 64-bit literal operands)
+    ChainK<Real> K = chain_consts<Real>();
+    HoverConst<Real> Cp = C;
+    if constexpr (sizeof(Real) == 8) {
+        pin_all(K);
+        pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass); pin(Cp.ang_max);
+        pin(Cp.ixx); pin(Cp.iyy); pin(Cp.izz); pin(Cp.inv_ixx); pin(Cp.inv_iyy); pin(Cp.inv_izz);
+        pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
+    }
+    // into the body frame: ω, the thrust axis (third column of the cached link basis) and its
+    // body coordinates; the loop carries these, not the matrices
+    Chain<Real> st{};
+    {
+        const M3<Real> R = rot_fm(b.q);
+        const M3<Real> Rs = lag ? rot_fm(b.ql) : R;
+        st.wb = mulT(R, b.w);
+        st.zc = col2(R);
+        st.zs = col2(Rs);
+        st.m3 = lag ? mulT(R, st.zs) : v3(Real(0), Real(0), Real(1));
+        if constexpr (DRAG) {
+            st.R = R;
+            st.Rs = Rs;
+        }
+    }
+    st.wn = hsqrt_nn_(dot(b.w, b.w), K);
+    st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
+    bool touched = false;
+    auto substep = [&]() {
+        if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
+        else touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
+    };
+    if constexpr (SC > 0) {
+#pragma unroll
+        for (int s = 0; s < SC; ++s) substep();
+    } else {
+        for (int s = 0; s < C.S; ++s) substep();
+    }
+    b.w = mul(rot_fm(b.q), st.wb);   // state, obs and the stored link_quat stay in the world frame
+    return touched;
+}
+
 // ------------------------------------------------------------------------------------------
 // env.step kernel: lane = env; B (ring length) is a template parameter so the ring lives
 // in registers
@@ -905,55 +979,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
         }
     } else {
-        Real sum_f = 0, t2 = 0;
-        V3<Real> P = v3(Real(0), Real(0), Real(0));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const Real r2 = rpm[i] * rpm[i];
-            const Real f = r2 * C.kf;
-            sum_f += f;
-            P = P + v3(f * C.px[i], f * C.py[i], f * C.pz[i]);
-            t2 += (i & 1) ? -r2 : r2;
-        }
-        const Real tau_z = t2 * C.km;    // KM*(rpm0^2 - rpm1^2 + rpm2^2 - rpm3^2), IROS sign
-        // the chain's constants in VGPRs for the whole loop (fp64: no 64-bit literal operands)
-        ChainK<Real> K = chain_consts<Real>();
-        HoverConst<Real> Cp = C;
-        if constexpr (sizeof(Real) == 8) {
-            pin_all(K);
-            pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass); pin(Cp.ang_max);
-            pin(Cp.ixx); pin(Cp.iyy); pin(Cp.izz); pin(Cp.inv_ixx); pin(Cp.inv_iyy); pin(Cp.inv_izz);
-            pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
-        }
-        // into the body frame: ω, the thrust axis (third column of the cached link basis) and its
-        // body coordinates; the loop carries these, not the matrices
-        Chain<Real> st{};
-        {
-            const M3<Real> R = rot_fm(b.q);
-            const M3<Real> Rs = lag ? rot_fm(b.ql) : R;
-            st.wb = mulT(R, b.w);
-            st.zc = col2(R);
-            st.zs = col2(Rs);
-            st.m3 = lag ? mulT(R, st.zs) : v3(Real(0), Real(0), Real(1));
-            if constexpr (DRAG) {
-                st.R = R;
-                st.Rs = Rs;
-            }
-        }
-        st.wn = hsqrt_nn_(dot(b.w, b.w), K);
-        st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
-        auto substep = [&]() {
-            touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
-        };
-        if constexpr (SC > 0) {
-#pragma unroll
-            for (int s = 0; s < SC; ++s) substep();
-        } else {
-            for (int s = 0; s < C.S; ++s) substep();
-        }
-        b.w = mul(rot_fm(b.q), st.wb);   // state, obs and the stored link_quat stay in the world frame
+        touched = pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{});
     }
     RACE_MARK(t2);
     if (touched && a.contact_count && (!split || threadIdx.x == 0)) atomicAdd(a.contact_count, 1);

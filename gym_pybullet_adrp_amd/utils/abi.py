@@ -12,7 +12,7 @@ MAX_OBSTACLES = 4
 
 OK, ERR_INVALID, ERR_DEVICE, ERR_OOM = 0, -1, -2, -3
 
-TASK_HOVER, TASK_RACE = 0, 1
+TASK_HOVER, TASK_RACE, TASK_MULTIHOVER = 0, 1, 2
 PHYS_PYB, PHYS_DYN, PHYS_PYB_GND, PHYS_PYB_DRAG, PHYS_PYB_DW, PHYS_PYB_GND_DRAG_DW = range(6)
 ACT_RPM, ACT_ONE_D_RPM, ACT_FULLSTATE, ACT_PID, ACT_VEL, ACT_ONE_D_PID = 0, 1, 2, 3, 4, 5
 MATH_RCP, MATH_RSQ, MATH_SQRT, MATH_SIN_SMALL, MATH_COS_SMALL, MATH_ATAN2, MATH_ASIN, MATH_EXP = range(8)   # adrp_math_probe

@@ -102,7 +102,7 @@ except ImportError:  # pragma: no cover
 
 
 class AviaryVecEnv(_VecEnvBase):
-    """SB3 VecEnv over one batched aviary (HoverAviary / MultiRaceAviary of this package)."""
+    """SB3 VecEnv over one batched aviary (HoverAviary / MultiHoverAviary / MultiRaceAviary of this package)."""
 
     def __init__(self, env, as_torch=False, zero_copy=None, ring=3, packed=None, terminal_rows=None, direct=None):
         self.env = env
@@ -428,6 +428,13 @@ def HoverAviaryVec(n_envs=1, as_torch=False, zero_copy=None, **env_kwargs):
     """``make_vec_env(HoverAviary, env_kwargs=..., n_envs=...)`` counterpart"""
     from .envs.hover import HoverAviary
     return AviaryVecEnv(HoverAviary(num_envs=n_envs, **env_kwargs), as_torch=as_torch, zero_copy=zero_copy)
+
+
+def MultiHoverAviaryVec(n_envs=1, as_torch=False, zero_copy=None, **env_kwargs):
+    """``make_vec_env(MultiHoverAviary, env_kwargs=..., n_envs=...)`` counterpart (examples/learn.py:59-63):
+    per-env spaces of shape (num_drones, .), one reward / done per env"""
+    from .envs.multihover import MultiHoverAviary
+    return AviaryVecEnv(MultiHoverAviary(num_envs=n_envs, **env_kwargs), as_torch=as_torch, zero_copy=zero_copy)
 
 
 def MultiRaceAviaryVec(n_envs=1, as_torch=False, zero_copy=None, **env_kwargs):

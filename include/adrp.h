@@ -52,6 +52,14 @@ extern "C" {
 /* adrp_config.task */
 #define ADRP_TASK_HOVER 0       /* HoverAviary (envs/HoverAviary.py) */
 #define ADRP_TASK_RACE 1        /* MultiRaceAviary (envs/MultiRaceAviary.py) */
+/* MultiHoverAviary (envs/MultiHoverAviary.py): num_drones 1..8 drones per env, RPM / ONE_D_RPM actions.
+ * The config is HoverAviary's with num_drones and init_xyz[n] / init_rpy[n] per drone; the targets are
+ * derived, TARGET_POS[n] = init_xyz[n] + (0, 0, 1/(n+1)) (MultiHoverAviary.py:71), target_pos is ignored.
+ * obs [E,N,12+B*A], action [E,N,A], reward / terminated / truncated [E] (sums / any over the env's
+ * drones, bounds 2.0); an env's drones reset together and the action ring of a reset env is cleared.
+ * Snapshot: HoverAviary's fields, [field][E*N], column e*N+n; the per-env ints (step_counter, episode,
+ * ring_head) are replicated on the env's columns and adrp_set_state takes drone 0's. */
+#define ADRP_TASK_MULTIHOVER 2
 
 /* adrp_config.physics — utils/enums.py:18-26 (Physics) */
 #define ADRP_PHYS_PYB 0
@@ -190,8 +198,9 @@ typedef struct adrp_handle adrp_t;
 /* ABI version of the loaded library (must equal ADRP_ABI_VERSION). */
 int adrp_abi_version(void);
 
-/* Fill *cfg with the reference defaults for `task` (HoverAviary or MultiRaceAviary,
- * CF2X = cf2x_IROS.urdf constants, level0 track for RACE). */
+/* Fill *cfg with the reference defaults for `task` (HoverAviary, MultiRaceAviary or MultiHoverAviary,
+ * CF2X = cf2x_IROS.urdf constants, level0 track for RACE; MULTIHOVER: the hover default with two
+ * drones at init_xyz[n] = (4Ln, 4Ln, COLLISION_H/2 - COLLISION_Z_OFFSET + 0.1), BaseAviary.py:194-197). */
 int adrp_default_config(int task, adrp_config* cfg);
 
 /* Create a handle on GPU `device`; allocates all state in HBM. */
@@ -257,7 +266,9 @@ int adrp_set_state(adrp_t* h, const void* f_dev, const int32_t* i_dev, void* str
 /* Name of the step-kernel instantiation a config selects (no device needed), e.g.
  * "hover_step<f32,PYB,A4,B15,cf2x>": "cf2x" = per-config constants compiled in (the
  * reference default drone at 240/30 Hz, chosen only when the config's derived constants
- * are bit-identical), "generic" = read from the handle's device-resident block. */
+ * are bit-identical), "generic" = read from the handle's device-resident block.
+ * MultiHoverAviary: "multihover_step<f32,PYB,A4,G2>", G = the lane-group width, the next power of two
+ * >= num_drones (one lane per drone, a group per env). */
 const char* adrp_kernel_name(const adrp_config* cfg);
 /* the instantiation this handle launches now (after adrp_enable_commands a race handle runs the
    command-mode kernel, "...,CMD>"; ADRP_RACE_QUAD as read at create) */
