@@ -247,15 +247,13 @@ def plane_contact(fo, names):
     return low < 1e-6
 
 
-def range_flags_ok(cfg, obs_g, obs_o, f):
-    """in-range flags may differ only within 1e-4 m of the 0.45 m range"""
-    E, N = obs_o.shape[:2]
+def range_flags_ok(obs_g, obs_o):
+    """the in-range flags of every gate (obs 28:32) and obstacle (44:48) equal the oracle's exactly:
+    no exemption near the 0.45 m range (tests/test_race_scenes_gpu.py puts drones within 3e-4 m of it)"""
     bad = np.argwhere(obs_g[..., 28:32] != obs_o[..., 28:32])
-    for e, n, g in bad:
-        pos, quat = obs_o[e, n, :3].astype(float), None
-        raise AssertionError(f"gate flag mismatch env {e} drone {n} gate {g}")
+    assert len(bad) == 0, f"gate flag mismatch (env, drone, gate) {bad[:4]}"
     bad = np.argwhere(obs_g[..., 44:48] != obs_o[..., 44:48])
-    assert len(bad) == 0, f"obstacle flag mismatch {bad[:4]}"
+    assert len(bad) == 0, f"obstacle flag mismatch (env, drone, obstacle) {bad[:4]}"
 
 
 @pytest.mark.parametrize("level,N,physics,mode,reward", CASES)
@@ -301,7 +299,7 @@ def test_teacher_forced_step(level, N, physics, mode, reward, precision):
             worst[g] = max(worst.get(g, 0), v)
         np.testing.assert_allclose(og[..., :3], obs_o[..., :3], rtol=1e-4, atol=1e-4)
         np.testing.assert_array_equal(og[..., 48], obs_o[..., 48])
-        range_flags_ok(env.cfg, og, obs_o, None)
+        range_flags_ok(og, obs_o)
         np.testing.assert_allclose(og[..., 12:28], obs_o[..., 12:28], atol=1e-5)
         np.testing.assert_allclose(og[..., 32:44], obs_o[..., 32:44], atol=1e-5)
         if mode == RaceMode.COMPETE:
