@@ -100,6 +100,8 @@ def load():
     # (every entry point include/adrp.h declares is bound: a library without one fails here, loudly)
     lib.adrp_policy_create2.argtypes = [I, I, I, I, I, I, P, P, P, P, P, P, ctypes.POINTER(P)]
     lib.adrp_policy_create2.restype = I
+    lib.adrp_policy_fragments.argtypes = [I, I, I, I, P, P, P, P, P, P, I, P, I, P]
+    lib.adrp_policy_fragments.restype = I
     lib.adrp_policy_set_critic.argtypes = [P] + [P] * 7
     lib.adrp_policy_set_critic.restype = I
     lib.adrp_policy_sample.argtypes = [P, P, I, I, I, ctypes.c_uint64, ctypes.c_uint32, P, P, P, P, P, P]

@@ -23,6 +23,7 @@ struct adrp_policy {
     int device = 0;
     int in_dim = 0, h1 = 0, h2 = 0, relu = 0, act_dim = 4;
     int row_tiles = 0;       // 16-row tiles per block (ADRP_POLICY_RT; 0 = default)
+    int wide = 0;            // served by the wide kernels: in_dim > 64, act_dim > 4 or ADRP_POLICY_WIDE=1
     PolicyLayout L{};
     float* blob = nullptr;   // device fragment blob
     PolicyLayout Lc{};       // critic (adrp_policy_set_critic)
@@ -31,18 +32,32 @@ struct adrp_policy {
 };
 
 // Pre-permute the Linear weights (torch layout [out][in], row-major) into the per-lane MFMA
-// fragments policy_kernel reads (see policy_kernel.h for the k order).
-static std::vector<float> build_blob(int in_dim, int H1, int H2, const float* w1, const float* b1, const float* w2,
-                                     const float* b2, const float* w3, const float* b3, PolicyLayout* L, int n_out = 4) {
-    const int T1 = H1 / 16, T2 = H2 / 16, S1 = kPolicyS1;
+// fragments policy_kernel reads (see policy_kernel.h for the k order).  wide: layer 1 holds
+// ceil(in_dim / 4) k-steps rounded up to a whole chunk of kPolicyChunk (zero weights beyond in_dim)
+// instead of kPolicyS1; either way layer 3 and b3 hold ceil(n_out / 16) tiles (zero rows beyond
+// n_out).  A policy inside the narrow box (in_dim <= 64, n_out <= 16) gets the same blob both ways.
+static void policy_layout(int in_dim, int H1, int H2, int n_out, bool wide, PolicyLayout* L) {
+    const int T1 = H1 / 16, T2 = H2 / 16, T3 = (n_out + 15) / 16;
+    const int S1 = wide ? ((in_dim + 3) / 4 + kPolicyChunk - 1) / kPolicyChunk * kPolicyChunk : kPolicyS1;
     L->in_dim = in_dim;
     L->f1 = 0;
     L->f2 = L->f1 + T1 * S1 * 64;
     L->f3 = L->f2 + T2 * T1 * 4 * 64;
-    L->b1 = L->f3 + T2 * 4 * 64;
+    L->b1 = L->f3 + T3 * T2 * 4 * 64;
     L->b2 = L->b1 + H1;
     L->b3 = L->b2 + H2;
-    L->total = (L->b3 + 16 + 3) & ~3;
+    L->total = (L->b3 + 16 * T3 + 3) & ~3;
+    L->s1 = S1;
+    L->t3 = T3;
+    L->n_out = n_out;
+    L->wide = wide ? 1 : 0;
+}
+
+static std::vector<float> build_blob(int in_dim, int H1, int H2, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, const float* w3, const float* b3, PolicyLayout* L, int n_out = 4,
+                                     bool wide = false) {
+    policy_layout(in_dim, H1, H2, n_out, wide, L);
+    const int T1 = H1 / 16, T2 = H2 / 16, S1 = L->s1, T3 = L->t3;
     std::vector<float> v(L->total, 0.0f);
     for (int t = 0; t < T1; ++t)
         for (int s = 0; s < S1; ++s)
@@ -57,12 +72,13 @@ static std::vector<float> build_blob(int in_dim, int H1, int H2, const float* w1
                     const int out = 16 * u + (l & 15), k = 16 * t + 4 * (l >> 4) + i;
                     v[L->f2 + ((u * T1 + t) * 4 + i) * 64 + l] = w2[size_t(out) * H1 + k];
                 }
-    for (int u = 0; u < T2; ++u)
-        for (int i = 0; i < 4; ++i)
-            for (int l = 0; l < 64; ++l) {
-                const int out = l & 15, k = 16 * u + 4 * (l >> 4) + i;
-                v[L->f3 + (u * 4 + i) * 64 + l] = out < n_out ? w3[size_t(out) * H2 + k] : 0.0f;
-            }
+    for (int u3 = 0; u3 < T3; ++u3)
+        for (int u = 0; u < T2; ++u)
+            for (int i = 0; i < 4; ++i)
+                for (int l = 0; l < 64; ++l) {
+                    const int out = 16 * u3 + (l & 15), k = 16 * u + 4 * (l >> 4) + i;
+                    v[L->f3 + ((u3 * T2 + u) * 4 + i) * 64 + l] = out < n_out ? w3[size_t(out) * H2 + k] : 0.0f;
+                }
     memcpy(&v[L->b1], b1, sizeof(float) * H1);
     memcpy(&v[L->b2], b2, sizeof(float) * H2);
     memcpy(&v[L->b3], b3, sizeof(float) * n_out);
@@ -107,6 +123,36 @@ static hipError_t dispatch_t2(const adrp_policy_t* p, const float* obs, int rows
 
 static bool pow2_tiles(int h) { return h == 16 || h == 32 || h == 64 || h == 128; }
 
+static_assert(kPolicyMaxIn == 576 && kPolicyMaxOut == 32, "the refusals below name the bounds");
+static int check_shape(int in_dim, int hidden1, int hidden2, int act_dim, const float* w1, const float* b1, const float* w2,
+                       const float* b2, const float* w3, const float* b3) {
+    if (act_dim < 1 || act_dim > kPolicyMaxOut) return seterr(nullptr, ADRP_ERR_INVALID, "policy act_dim must be 1..32");
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return seterr(nullptr, ADRP_ERR_INVALID, "NULL weight pointer");
+    if (in_dim < 1 || in_dim > kPolicyMaxIn) return seterr(nullptr, ADRP_ERR_INVALID, "policy in_dim must be 1..576");
+    if (!pow2_tiles(hidden1) || !pow2_tiles(hidden2))
+        return seterr(nullptr, ADRP_ERR_INVALID, "policy hidden sizes must be 16, 32, 64 or 128");
+    return ADRP_OK;
+}
+
+// outside the narrow kernels' box, or forced (ADRP_POLICY_WIDE=1, read at create like ADRP_POLICY_RT)
+static bool wide_policy(int in_dim, int act_dim, bool forced) { return forced || in_dim > 4 * kPolicyS1 || act_dim > 4; }
+
+extern "C" int adrp_policy_fragments(int in_dim, int hidden1, int hidden2, int n_out, const float* w1, const float* b1,
+                                     const float* w2, const float* b2, const float* w3, const float* b3, int wide,
+                                     float* blob_out, int blob_cap, int layout_out[16]) {
+    if (const int rc = check_shape(in_dim, hidden1, hidden2, n_out, w1, b1, w2, b2, w3, b3)) return rc;
+    PolicyLayout L{};
+    const std::vector<float> blob = build_blob(in_dim, hidden1, hidden2, w1, b1, w2, b2, w3, b3, &L, n_out,
+                                               wide_policy(in_dim, n_out, wide != 0));
+    if (blob_out && blob_cap >= L.total) memcpy(blob_out, blob.data(), sizeof(float) * L.total);
+    if (layout_out) {
+        static_assert(sizeof(PolicyLayout) <= 16 * sizeof(int), "layout_out holds the PolicyLayout fields");
+        memset(layout_out, 0, 16 * sizeof(int));
+        memcpy(layout_out, &L, sizeof(PolicyLayout));
+    }
+    return L.total;
+}
+
 extern "C" int adrp_policy_create(int device, int in_dim, int hidden1, int hidden2, int activation, const float* w1,
                                   const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
                                   adrp_policy_t** out) {
@@ -127,12 +173,8 @@ extern "C" int adrp_policy_create2(int device, int in_dim, int hidden1, int hidd
                                    const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                    const float* b3, adrp_policy_t** out) {
     if (!out) return seterr(nullptr, ADRP_ERR_INVALID, "out is NULL");
-    if (act_dim < 1 || act_dim > 4) return seterr(nullptr, ADRP_ERR_INVALID, "policy act_dim must be 1..4");
     *out = nullptr;
-    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3) return seterr(nullptr, ADRP_ERR_INVALID, "NULL weight pointer");
-    if (in_dim < 1 || in_dim > 4 * kPolicyS1) return seterr(nullptr, ADRP_ERR_INVALID, "policy in_dim must be 1..64");
-    if (!pow2_tiles(hidden1) || !pow2_tiles(hidden2))
-        return seterr(nullptr, ADRP_ERR_INVALID, "policy hidden sizes must be 16, 32, 64 or 128");
+    if (const int rc = check_shape(in_dim, hidden1, hidden2, act_dim, w1, b1, w2, b2, w3, b3)) return rc;
     if (activation != ADRP_POLICY_TANH && activation != ADRP_POLICY_RELU)
         return seterr(nullptr, ADRP_ERR_INVALID, "policy activation must be TANH or RELU");
     int ndev = 0;
@@ -144,7 +186,10 @@ extern "C" int adrp_policy_create2(int device, int in_dim, int hidden1, int hidd
     p->in_dim = in_dim; p->h1 = hidden1; p->h2 = hidden2; p->relu = activation == ADRP_POLICY_RELU;
     p->act_dim = act_dim;
     if (const char* env = getenv("ADRP_POLICY_RT")) p->row_tiles = atoi(env);
-    const std::vector<float> blob = build_blob(in_dim, hidden1, hidden2, w1, b1, w2, b2, w3, b3, &p->L, act_dim);
+    const char* force = getenv("ADRP_POLICY_WIDE");
+    p->wide = wide_policy(in_dim, act_dim, force && atoi(force) != 0);
+    const std::vector<float> blob =
+        build_blob(in_dim, hidden1, hidden2, w1, b1, w2, b2, w3, b3, &p->L, act_dim, p->wide != 0);
     DeviceGuard g(device);
     if (hipMalloc((void**)&p->blob, blob.size() * sizeof(float)) != hipSuccess) {
         delete p;
@@ -176,7 +221,8 @@ extern "C" int adrp_policy_set_critic(adrp_policy_t* p, const float* vw1, const 
     DeviceGuard g(p->device);
     if (p->critic) { hipFree(p->critic); p->critic = nullptr; }
     if (p->log_std) { hipFree(p->log_std); p->log_std = nullptr; }
-    const std::vector<float> blob = build_blob(p->in_dim, p->h1, p->h2, vw1, vb1, vw2, vb2, vw3, vb3, &p->Lc, 1);
+    const std::vector<float> blob = build_blob(p->in_dim, p->h1, p->h2, vw1, vb1, vw2, vb2, vw3, vb3, &p->Lc, 1,
+                                               p->wide != 0);
     int rc = upload(blob, &p->critic);
     if (rc == ADRP_OK) rc = upload(std::vector<float>(log_std, log_std + p->act_dim), &p->log_std);
     if (rc != ADRP_OK) return seterr(nullptr, rc, "adrp_policy_set_critic: upload failed");
@@ -221,7 +267,8 @@ extern "C" int adrp_policy_sample(adrp_policy_t* p, const float* obs_dev, int ro
     DeviceGuard g(p->device);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    switch (p->h1 / 16) {
+    if (p->wide) e = policy_sample_wide_launch(p->h1, p->h2, p->relu, a, s);
+    else switch (p->h1 / 16) {
         case 1: e = sample_t2<1>(p, a, s); break;
         case 2: e = sample_t2<2>(p, a, s); break;
         case 4: e = sample_t2<4>(p, a, s); break;
@@ -234,17 +281,22 @@ extern "C" int adrp_policy_sample(adrp_policy_t* p, const float* obs_dev, int ro
 extern "C" int adrp_policy_act(adrp_policy_t* p, const float* obs_dev, int rows, int obs_stride, int mode,
                                float* act_dev, void* stream) {
     if (!p || !obs_dev || !act_dev) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_policy_act: NULL argument");
-    if (p->act_dim != 4) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_policy_act: 4 actions (adrp_policy_sample takes 1..4)");
     if (rows < 0 || obs_stride < p->in_dim) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_policy_act: rows / obs_stride");
     if (mode != ADRP_POLICY_RAW && mode != ADRP_POLICY_RELATIVE && mode != ADRP_POLICY_ABSOLUTE)
         return seterr(nullptr, ADRP_ERR_INVALID, "adrp_policy_act: mode");
+    if (mode != ADRP_POLICY_RAW && p->act_dim != 4)
+        return seterr(nullptr, ADRP_ERR_INVALID, "adrp_policy_act: RELATIVE / ABSOLUTE need 4 actions (RAW takes 1..32)");
     if (mode == ADRP_POLICY_RELATIVE && p->in_dim < 6)
         return seterr(nullptr, ADRP_ERR_INVALID, "RELATIVE mode reads the pose from obs[0:3] and obs[5]");
     if (rows == 0) return ADRP_OK;
     DeviceGuard g(p->device);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e;
-    switch (p->h1 / 16) {
+    // the narrow kernel stores float4 rows: a narrow policy with 1..3 outputs goes through the wide
+    // kernel, which reads the same blob (s1 = 16, one output tile) and stores [rows][act_dim]
+    if (p->wide || p->act_dim != 4)
+        e = policy_wide_launch(p->blob, p->L, p->h1, p->h2, p->relu, obs_dev, rows, obs_stride, act_dev, mode, s);
+    else switch (p->h1 / 16) {
         case 1: e = dispatch_t2<1>(p, obs_dev, rows, obs_stride, act_dev, mode, s); break;
         case 2: e = dispatch_t2<2>(p, obs_dev, rows, obs_stride, act_dev, mode, s); break;
         case 4: e = dispatch_t2<4>(p, obs_dev, rows, obs_stride, act_dev, mode, s); break;

@@ -30,6 +30,9 @@ ACTOR_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.b
 CRITIC_KEYS = ("mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
                "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias",
                "value_net.weight", "value_net.bias", "log_std")
+# csrc/policy_kernel.h PolicyLayout, in declaration order (adrp_policy_fragments' layout_out)
+LAYOUT_FIELDS = ("in_dim", "f1", "f2", "f3", "b1", "b2", "b3", "total", "s1", "t3", "n_out", "wide")
+MAX_OUT = 32          # csrc/policy_kernel.h kPolicyMaxOut
 
 
 def load_sb3_zip(path, critic=False):
@@ -45,8 +48,25 @@ def load_sb3_zip(path, critic=False):
     return {k: sd[k].float().numpy() for k in keys}, activation
 
 
+def policy_fragments(weights, wide=False):
+    """The MFMA fragment blob a policy with these ACTOR_KEYS weights is uploaded as, and its layout
+    (include/adrp.h adrp_policy_fragments; host only, needs no GPU) -> (float32 blob, {field: int})"""
+    lib = _lib.load()
+    w = [np.ascontiguousarray(weights[k], np.float32) for k in ACTOR_KEYS]
+    shape = (w[0].shape[1], w[0].shape[0], w[2].shape[0], w[4].shape[0])
+    ptr = [a.ctypes.data_as(ctypes.c_void_p) for a in w]
+    layout = (ctypes.c_int * 16)()
+    n = lib.adrp_policy_fragments(*shape, *ptr, int(bool(wide)), None, 0, layout)
+    if n < 0:
+        raise ValueError(f"adrp_policy_fragments: {lib.adrp_last_error(None).decode()}")
+    blob = np.zeros(n, np.float32)
+    lib.adrp_policy_fragments(*shape, *ptr, int(bool(wide)), blob.ctypes.data_as(ctypes.c_void_p), n, layout)
+    return blob, dict(zip(LAYOUT_FIELDS, layout))
+
+
 class DevicePolicy:
-    """Actor of an SB3 MlpPolicy with two hidden layers, on one GPU.
+    """Actor of an SB3 MlpPolicy with two hidden layers, on one GPU: in_dim 1..576, 1..32 outputs
+    (a joint MultiHoverAviary agent: N x D inputs, N x A outputs).
 
     ``mode``: "raw" (the clipped action), "relative" (RLController: a[3] = 0, setpoint =
     obs[[0,1,2,5]] + a*[1,1,1,pi], yaw map2pi) or "absolute" (RLControllerTwoGates:
@@ -58,8 +78,8 @@ class DevicePolicy:
             raise _lib.AdrpError("no HIP device visible: libadrp has no CPU fallback")
         w = [np.ascontiguousarray(weights[k], np.float32) for k in ACTOR_KEYS]
         (w1, b1, w2, b2, w3, b3) = w
-        if not 1 <= w3.shape[0] <= 4:
-            raise ValueError("the action_net must have 1..4 outputs")
+        if not 1 <= w3.shape[0] <= MAX_OUT:
+            raise ValueError(f"the action_net must have 1..{MAX_OUT} outputs")
         self.act_dim = w3.shape[0]
         if self.act_dim != 4 and mode != "raw":
             raise ValueError("RLController transforms need the 4 outputs (x, y, z, yaw)")
@@ -123,13 +143,15 @@ class DevicePolicy:
 
     def act(self, obs, out=None):
         """obs [..., D] float32 on the device (D >= in_dim; the first in_dim columns are the
-        policy input) -> setpoints [..., 4] (written into ``out`` if given)"""
+        policy input) -> setpoints [..., 4], in raw mode the clipped actions [..., act_dim]
+        (written into ``out`` if given)"""
         rows = obs.numel() // obs.shape[-1]
         if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()):
             raise ValueError("obs must be a contiguous float32 device tensor")
+        width = self.act_dim if self.mode == MODES["raw"] else 4
         if out is None:
-            out = torch.empty(obs.shape[:-1] + (4,), dtype=torch.float32, device=obs.device)
-        assert out.is_contiguous() and out.numel() == rows * 4
+            out = torch.empty(obs.shape[:-1] + (width,), dtype=torch.float32, device=obs.device)
+        assert out.is_contiguous() and out.numel() == rows * width
         rc = self.lib.adrp_policy_act(self.h, obs.data_ptr(), rows, obs.shape[-1], self.mode, out.data_ptr(),
                                       _lib._raw_stream(obs.device.index))
         if rc != 0:
@@ -149,14 +171,26 @@ class DevicePolicy:
 
 
 def rollout(env, policy, steps, act=None):
-    """Closed-loop MultiRaceAviary rollout entirely on the device: obs -> policy -> setpoints
-    -> env.step, ``steps`` times (env auto-resets done envs).  Returns the last step's outputs."""
+    """Closed-loop rollout entirely on the device: obs -> policy -> setpoints / actions -> env.step,
+    ``steps`` times (env auto-resets done envs).  Returns the last step's outputs.
+
+    A policy whose ``in_dim`` is the env's whole joint row (``NUM_DRONES * D``: SB3's MlpPolicy on
+    MultiHoverAviary) reads ``obs.view(E, N D)`` and its ``[E, N A]`` result steps the env as
+    ``[E, N, A]`` (row-major [drone][action], SB3's reshape of the flat action); any other policy acts
+    per drone row (MultiRaceAviary's RLController setting)."""
     obs = env._obs if hasattr(env, "_obs") else env.reset()[0]
-    if act is None:
-        act = torch.empty(obs.shape[:-1] + (4,), dtype=torch.float32, device=obs.device)
+    joint = obs.dim() == 3 and obs.shape[1] > 1 and policy.in_dim == obs.shape[1] * obs.shape[2]
+    width = policy.act_dim if policy.mode == MODES["raw"] else 4
+    if joint:
+        if width != obs.shape[1] * env._act_shape[-1]:
+            raise ValueError("a joint policy emits NUM_DRONES * A actions")
+        if act is None:
+            act = torch.empty(tuple(env._act_shape), dtype=torch.float32, device=obs.device)
+    elif act is None:
+        act = torch.empty(obs.shape[:-1] + (width,), dtype=torch.float32, device=obs.device)
     out = None
     for _ in range(steps):
-        policy.act(obs, out=act)
+        policy.act(obs.view(obs.shape[0], -1) if joint else obs, out=act)
         out = env.step(act)
         obs = out[0]
     return out

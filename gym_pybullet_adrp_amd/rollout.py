@@ -15,30 +15,45 @@ tensor resident on the GPU:
   time limit (and not a termination), SB3 collect_rollouts;
 * ``adrp_gae`` for the advantages and returns.
 
-One agent per env: HoverAviary (learn.py's task) or a one-drone MultiRaceAviary (the RLController
-setting).  ``collect`` can be captured in one HIP graph (every pointer is fixed per step).
+One agent per env: HoverAviary (learn.py's task), a one-drone MultiRaceAviary (the RLController
+setting), or MultiHoverAviary (learn.py --multiagent true) as the one joint agent SB3's MlpPolicy
+makes of it: the (N, D) observation flattened to N D inputs, N A outputs reshaped row-major to
+(N, A), one reward / done per env.  ``collect`` can be captured in one HIP graph (every pointer is
+fixed per step).
 """
 import torch
 
 from . import _lib
+from .envs.multihover import MultiHoverAviary
 
 
 class RolloutCollector:
     """``n_steps`` x ``num_envs`` PPO rollout buffer on the env's device.
 
     policy: ``DevicePolicy`` with a critic (``set_critic`` / ``from_zip(critic=True)``), its input
-    the first ``policy.in_dim`` obs floats of the agent's row."""
+    the first ``policy.in_dim`` obs floats of the agent's row; for MultiHoverAviary the whole joint
+    row (``in_dim == NUM_DRONES * D``, ``act_dim == NUM_DRONES * A``, raw mode)."""
 
     def __init__(self, env, policy, n_steps, gamma=0.99, gae_lambda=0.95, seed=0):
         if not policy.has_critic:
             raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
-        if env.NUM_DRONES != 1:
-            raise ValueError("one agent per env: HoverAviary or MultiRaceAviary(num_drones=1)")
+        N = env.NUM_DRONES
+        if N != 1 and not isinstance(env, MultiHoverAviary):
+            raise ValueError("one agent per env: HoverAviary, MultiRaceAviary(num_drones=1), or MultiHoverAviary "
+                             "as one joint agent (per-drone agents of a multi-drone race are not collected)")
+        # the agent's row: all N drones' rows side by side (SB3 flattens the (N, D) observation)
+        D, A = N * env.h.D, policy.act_dim
+        if N != 1:
+            if policy.in_dim != D:
+                raise ValueError(f"a joint MultiHoverAviary policy reads NUM_DRONES * D = {D} inputs, not {policy.in_dim}")
+            if policy.mode != 0 or A != N * env.h.A:
+                raise ValueError(f"a joint MultiHoverAviary policy emits NUM_DRONES * A = {N * env.h.A} raw actions")
+        elif policy.in_dim > D:
+            raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
         self.env, self.policy = env, policy
         self.T, self.E = int(n_steps), env.num_envs
         self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
         dev = env.device
-        D, A = env.h.D, policy.act_dim
         f32 = dict(dtype=torch.float32, device=dev)
         self.obs = torch.zeros((self.T, self.E, D), **f32)
         self.actions = torch.zeros((self.T, self.E, A), **f32)

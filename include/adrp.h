@@ -332,7 +332,11 @@ int adrp_race_reset_counts(adrp_t* h, int32_t* out, int reset);
  * action_net, clip to the [-1, 1] Box).  Weights are host float32 arrays in torch Linear
  * layout ([out][in] row-major): the policy.pth tensors mlp_extractor.policy_net.{0,2}.* and
  * action_net.*.  obs rows are the first in_dim floats of each obs_stride-wide row (e.g.
- * adrp_step's obs_dev with rows = E*N); act_dev receives float [rows][4].
+ * adrp_step's obs_dev with rows = E*N); act_dev receives float [rows][4] (RELATIVE / ABSOLUTE,
+ * and RAW with 4 actions) or [rows][act_dim] (RAW).  Policies with in_dim <= 64 and act_dim <= 4
+ * run the narrow kernels; wider ones (in_dim <= 576 = ADRP_MAX_DRONES x 72, the joint
+ * MultiHoverAviary row SB3's MlpPolicy flattens; act_dim <= 32) the wide kernels, as does every
+ * policy created with ADRP_POLICY_WIDE=1 in the environment (csrc/policy_kernel.h).
  * --------------------------------------------------------------------------------------- */
 #define ADRP_POLICY_TANH 0          /* SB3 MlpPolicy default activation_fn (nn.Tanh) */
 #define ADRP_POLICY_RELU 1          /* policy_kwargs activation_fn=nn.ReLU (twogates.zip) */
@@ -342,17 +346,31 @@ int adrp_race_reset_counts(adrp_t* h, int32_t* out, int reset);
 
 typedef struct adrp_policy adrp_policy_t;
 
-/* hidden1, hidden2 in {16, 32, 64, 128}; in_dim 1..64 */
+/* hidden1, hidden2 in {16, 32, 64, 128}; in_dim 1..576; 4 actions */
 int adrp_policy_create(int device, int in_dim, int hidden1, int hidden2, int activation,
                        const float* w1, const float* b1, const float* w2, const float* b2,
                        const float* w3, const float* b3, adrp_policy_t** out);
 int adrp_policy_act(adrp_policy_t* p, const float* obs_dev, int rows, int obs_stride, int mode,
                     float* act_dev, void* stream);
 void adrp_policy_destroy(adrp_policy_t* p);
-/* act_dim 1..4 (HoverAviary ONE_D_RPM policies: 1); adrp_policy_act needs 4, adrp_policy_sample any */
+/* act_dim 1..32: the action_net's outputs (HoverAviary ONE_D_RPM 1, RPM 4; a joint MultiHoverAviary
+ * agent N x A, row-major [drone][action] as SB3 reshapes the flat action).  RELATIVE / ABSOLUTE need
+ * act_dim == 4; RAW takes any, in adrp_policy_act and adrp_policy_sample alike. */
 int adrp_policy_create2(int device, int in_dim, int hidden1, int hidden2, int act_dim, int activation,
                         const float* w1, const float* b1, const float* w2, const float* b2,
                         const float* w3, const float* b3, adrp_policy_t** out);
+
+/* The fragment blob a policy of this shape is uploaded as (host only, no device needed): returns its
+ * size in floats or a negative ADRP_ERR_*; writes it to blob_out when blob_cap (floats) suffices, and
+ * the layout (csrc/policy_kernel.h PolicyLayout, fields in declaration order: in_dim, f1, f2, f3, b1,
+ * b2, b3, total, s1, t3, n_out, wide; the rest 0) to layout_out unless NULL.  wide != 0: the wide
+ * kernels' layout even inside the narrow box (what ADRP_POLICY_WIDE=1 uploads); 0: what
+ * adrp_policy_create2 picks.  Lane l of fragment (t, s) of layer 1 holds W1[16 t + (l & 15)][4 s + (l >> 4)],
+ * of fragment (u, t, i) of layer 2 W2[16 u + (l & 15)][16 t + 4 (l >> 4) + i], of fragment (u3, u, i) of
+ * layer 3 W3[16 u3 + (l & 15)][16 u + 4 (l >> 4) + i]; zeros beyond in_dim / n_out. */
+int adrp_policy_fragments(int in_dim, int hidden1, int hidden2, int n_out, const float* w1, const float* b1,
+                          const float* w2, const float* b2, const float* w3, const float* b3, int wide,
+                          float* blob_out, int blob_cap, int layout_out[16]);
 
 /* ---------------------------------------------------------------------------------------
  * On-device PPO rollout step (examples/learn.py:72-94 trains PPO): what SB3's
@@ -361,8 +379,9 @@ int adrp_policy_create2(int device, int in_dim, int hidden1, int hidden2, int ac
  * mean (as adrp_policy_act), the critic mlp_extractor.value_net (in_dim -> hidden1 -> hidden2, the
  * same activation) + value_net (-> 1), a DiagGaussianDistribution sample a = mean +
  * exp(log_std) eps and log_prob = sum_i Normal(mean_i, std_i).log_prob(a_i).  eps ~ N(0, 1): one
- * Philox4x32-10 block per row, counter {row, counter, 0x504f4c00, 0} keyed by seed, Box-Muller of
- * its word pairs (the race action noise's IEEE float form).  Replaces, batched on the device,
+ * Philox4x32-10 block per (row, output quad q), counter {row, counter, 0x504f4c00, q} keyed by seed,
+ * Box-Muller of its word pairs (the race action noise's IEEE float form) for outputs 4q .. 4q+3;
+ * log_prob is the float32 sum in ascending output index.  Replaces, batched on the device,
  * policy(obs_tensor) inside collect_rollouts plus the np.clip of the actions it sends the env.
  * adrp_policy_set_critic: value_net.{0,2}.* / value_net.* in torch layout and log_std [act_dim].
  * adrp_policy_sample: action_dev [rows][act_dim] (the sample, what the rollout buffer stores),
