@@ -121,6 +121,11 @@ def load():
     if hasattr(lib, "adrp_math_probe"):      # (A/B runs may load an older build without it)
         lib.adrp_math_probe.argtypes = [I, P, P, I, P]
         lib.adrp_math_probe.restype = I
+    if hasattr(lib, "adrp_math_probe_v"):    # (likewise)
+        lib.adrp_math_probe_v_planes.argtypes = [I, ctypes.POINTER(I), ctypes.POINTER(I)]
+        lib.adrp_math_probe_v_planes.restype = I
+        lib.adrp_math_probe_v.argtypes = [I, I, P, P, I, P]
+        lib.adrp_math_probe_v.restype = I
     if lib.adrp_abi_version() != abi.ABI_VERSION:
         raise AdrpError(f"libadrp ABI {lib.adrp_abi_version()} != python mirror {abi.ABI_VERSION}")
     _lib = lib

@@ -627,16 +627,42 @@ __device__ __forceinline__ V3<Real> euler_xyz(Q4<Real> q) {
             atan2_(Real(2) * (q.x * q.y + q.w * q.z), squ + sqx - sqy - sqz)};
 }
 
+// The atan2 / asin arguments of getEulerFromQuaternion's generic branch: sarg = sin pitch, roll =
+// atan2(y0, x0), yaw = atan2(y2, x2).  Contraction is pinned here to the C rule (a*b+c fused only inside
+// one source expression), whatever the translation unit's mode.  hipcc's default (fast) fuses after
+// inlining, and two inlined copies of these expressions -- the arms of a wave-uniform gimbal vote, the
+// one-angle-per-lane restatements -- then differed in the last bits of the arguments, up to 19 ulp (fp64)
+// and 47 ulp (fp32) of the angle near pitch +-pi/2 (tests/test_math_gpu.py::test_euler_vote_is_per_lane
+// in the probe TU, which has the race TUs' mode).  With the rule pinned every copy gives the same bits
+// (the hover TUs compile with this rule already: their results are unchanged).
+template <typename Real>
+struct EulerArgs {
+    Real sarg, y0, x0, y2, x2;
+};
+template <typename Real>
+__device__ __forceinline__ Real euler_sarg(Q4<Real> q) {
+#pragma clang fp contract(on)
+    return Real(-2) * (q.x * q.z - q.w * q.y);
+}
+template <typename Real>
+__device__ __forceinline__ EulerArgs<Real> euler_args(Q4<Real> q) {
+#pragma clang fp contract(on)
+    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
+    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
+    const Real y0 = Real(2) * (q.y * q.z + q.w * q.x), x0 = squ - sqx - sqy + sqz;
+    const Real y2 = Real(2) * (q.x * q.y + q.w * q.z), x2 = squ + sqx - sqy - sqz;
+    return {sarg, y0, x0, y2, x2};
+}
+
 // euler_xyz with the fast fp32 atan2/asin (controller input inside the sub-step loop)
 template <typename Real>
 __device__ __forceinline__ V3<Real> euler_xyz_fast(Q4<Real> q) {
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
+    const Real sarg = euler_sarg(q);
     const Real half_pi = Real(1.57079632679489661923);
     if (sarg <= Real(-0.99999)) return {Real(0), -half_pi, Real(2) * fatan2_(q.x, -q.y)};
     if (sarg >= Real(0.99999)) return {Real(0), half_pi, Real(2) * fatan2_(-q.x, q.y)};
-    return {fatan2_(Real(2) * (q.y * q.z + q.w * q.x), squ - sqx - sqy + sqz), fasin_(sarg),
-            fatan2_(Real(2) * (q.x * q.y + q.w * q.z), squ + sqx - sqy - sqz)};
+    const EulerArgs<Real> a = euler_args(q);
+    return {fatan2_(a.y0, a.x0), fasin_(a.sarg), fatan2_(a.y2, a.x2)};
 }
 
 // euler_xyz_fast with the gimbal-lock branches behind a wave-uniform test: the common path
@@ -644,11 +670,9 @@ __device__ __forceinline__ V3<Real> euler_xyz_fast(Q4<Real> q) {
 // that need the result active; inactive lanes do not vote)
 template <typename Real>
 __device__ __forceinline__ V3<Real> euler_xyz_fast_u(Q4<Real> q) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
-    if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) return euler_xyz_fast(q);
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    return {fatan2_(Real(2) * (q.y * q.z + q.w * q.x), squ - sqx - sqy + sqz), fasin_(sarg),
-            fatan2_(Real(2) * (q.x * q.y + q.w * q.z), squ + sqx - sqy - sqz)};
+    if (__builtin_expect(__any(fabs_(euler_sarg(q)) >= Real(0.99999)), 0)) return euler_xyz_fast(q);
+    const EulerArgs<Real> a = euler_args(q);
+    return {fatan2_(a.y0, a.x0), fasin_(a.sarg), fatan2_(a.y2, a.x2)};
 }
 
 // getQuaternionFromEuler (rpy extrinsic xyz)

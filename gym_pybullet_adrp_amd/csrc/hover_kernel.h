@@ -453,43 +453,40 @@ __device__ __forceinline__ void hover_reset_state(const HoverArgs<Real>& args, c
     hover_reset_draw(*args.r, args.seed, uint64_t(args.env_offset + e), TAG_HOVER_RESET, C, b, sc, ep);
 }
 
-// euler_xyz_fast_u's angles one at a time: the same expressions (the same contraction, so the same
-// bits) and the same wave-uniform gimbal-lock branch, for the HELP kernel's angle helpers
+// euler_xyz_fast_u's angles one at a time: the same arguments (euler_args, contraction pinned, so the
+// same bits) and the same wave-uniform gimbal-lock branch, for the HELP kernel's angle helpers
 template <typename Real>
 __device__ __forceinline__ Real euler_roll_u(Q4<Real> q) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
-    if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) return euler_xyz_fast(q).x;
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    return fatan2_(Real(2) * (q.y * q.z + q.w * q.x), squ - sqx - sqy + sqz);
+    if (__builtin_expect(__any(fabs_(euler_sarg(q)) >= Real(0.99999)), 0)) return euler_xyz_fast(q).x;
+    const EulerArgs<Real> a = euler_args(q);
+    return fatan2_(a.y0, a.x0);
 }
 template <typename Real>
 __device__ __forceinline__ Real euler_pitch_u(Q4<Real> q) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
+    const Real sarg = euler_sarg(q);
     if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) return euler_xyz_fast(q).y;
     return fasin_(sarg);
 }
 template <typename Real>
 __device__ __forceinline__ Real euler_yaw_u(Q4<Real> q) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
-    if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) return euler_xyz_fast(q).z;
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    return fatan2_(Real(2) * (q.x * q.y + q.w * q.z), squ + sqx - sqy - sqz);
+    if (__builtin_expect(__any(fabs_(euler_sarg(q)) >= Real(0.99999)), 0)) return euler_xyz_fast(q).z;
+    const EulerArgs<Real> a = euler_args(q);
+    return fatan2_(a.y2, a.x2);
 }
 
 // E = 1 persistent step (SPLIT): lane L evaluates Euler angle min(L, 2) of the (duplicated) env with
 // ONE atan2 -- roll (y0, x0), pitch (sarg, sqrt((1 - sarg)(1 + sarg)), the atan2 form of fasin_),
-// yaw (y2, x2) -- and the three come back by readlane: the same expressions as euler_xyz_fast_u, so
-// the same bits, for one atan2 on the chain instead of three
+// yaw (y2, x2) -- and the three come back by readlane: the same arguments as euler_xyz_fast_u
+// (euler_args), so the same bits, for one atan2 on the chain instead of three
 template <typename Real>
 __device__ __forceinline__ Real euler_axis_u(Q4<Real> q, int ax) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
+    const EulerArgs<Real> a = euler_args(q);
+    const Real sarg = a.sarg;
     if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) {
         const V3<Real> r = euler_xyz_fast(q);
         return ax == 0 ? r.x : (ax == 1 ? r.y : r.z);
     }
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    const Real y0 = Real(2) * (q.y * q.z + q.w * q.x), x0 = squ - sqx - sqy + sqz;
-    const Real y2 = Real(2) * (q.x * q.y + q.w * q.z), x2 = squ + sqx - sqy - sqz;
+    const Real y0 = a.y0, x0 = a.x0, y2 = a.y2, x2 = a.x2;
     Real x1;
     if constexpr (sizeof(Real) == 8) x1 = f64::sqrt((1.0 - sarg) * (1.0 + sarg));
     else x1 = __builtin_amdgcn_sqrtf((1.0f - sarg) * (1.0f + sarg));

@@ -102,20 +102,19 @@ __device__ __forceinline__ double grpq(double v, int k) {
 }
 
 // this lane's controller Euler angle (axis a = min(ql, 2)) of euler_xyz_fast_u(q): the same
-// atan2 / asin expressions, one per lane; the rare gimbal-lock branch evaluates all three
+// arguments (euler_args: contraction pinned, so both arms of the vote and the one-lane kernel's
+// euler_xyz_fast_u round alike), one atan2 per lane; the rare gimbal-lock branch evaluates all three
 template <typename Real>
 __device__ __forceinline__ Real euler_axis_q4(Q4<Real> q, int a) {
-    const Real sarg = Real(-2) * (q.x * q.z - q.w * q.y);
+    const EulerArgs<Real> e = euler_args(q);
+    const Real sarg = e.sarg;
     if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) {
         const V3<Real> r = euler_xyz_fast(q);
         return a == 0 ? r.x : (a == 1 ? r.y : r.z);
     }
-    const Real sqx = q.x * q.x, sqy = q.y * q.y, sqz = q.z * q.z, squ = q.w * q.w;
-    const Real y0 = Real(2) * (q.y * q.z + q.w * q.x), x0 = squ - sqx - sqy + sqz;
-    const Real y2 = Real(2) * (q.x * q.y + q.w * q.z), x2 = squ + sqx - sqy - sqz;
     // fasin_(sarg); the argument is > 0 here (|sarg| < 0.99999), the operands finite
     const Real x1 = hsqrt_nn_((Real(1) - sarg) * (Real(1) + sarg));
-    const Real yy = a == 0 ? y0 : (a == 1 ? sarg : y2), xx = a == 0 ? x0 : (a == 1 ? x1 : x2);
+    const Real yy = a == 0 ? e.y0 : (a == 1 ? sarg : e.y2), xx = a == 0 ? e.x0 : (a == 1 ? x1 : e.x2);
     return fatan2_nc_(yy, xx);
 }
 

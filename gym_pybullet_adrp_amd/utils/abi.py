@@ -20,6 +20,13 @@ MATH_SQRT_NN, MATH_RCP_NC, MATH_RSQ_NC, MATH_SIN_TINY, MATH_COS_TINY = 8, 9, 10,
 MATH_EXPMAP_SINC, MATH_EXPMAP_COS, MATH_QUAT_INV_NORM, MATH_NORMAL_Z0, MATH_NORMAL_Z1 = 13, 14, 15, 16, 17
 MATH_DIVC, MATH_SIN_FAST, MATH_COS_FAST = 18, 19, 20
 MATH_EXP_TAB, MATH_ATAN2_NC, MATH_FDIV_RCP = 21, 22, 23
+(MATHV_EULER_XYZ, MATHV_EULER_XYZ_FAST, MATHV_EULER_XYZ_FAST_U, MATHV_QUAT_FROM_EULER, MATHV_QUAT_FROM_EULER_FAST,
+ MATHV_FATAN2, MATHV_FASIN, MATHV_FEXP, MATHV_SMALL_SINCOS, MATHV_EXPMAP_SINC_COS, MATHV_QUAT_INV_NORM,
+ MATHV_CLAMP100_WV) = range(12)   # adrp_math_probe_v
+MATHV_PLANES = {MATHV_EULER_XYZ: (4, 3), MATHV_EULER_XYZ_FAST: (4, 3), MATHV_EULER_XYZ_FAST_U: (4, 3),
+                MATHV_QUAT_FROM_EULER: (3, 4), MATHV_QUAT_FROM_EULER_FAST: (3, 4), MATHV_FATAN2: (2, 1), MATHV_FASIN: (1, 1),
+                MATHV_FEXP: (1, 1), MATHV_SMALL_SINCOS: (1, 2), MATHV_EXPMAP_SINC_COS: (1, 2), MATHV_QUAT_INV_NORM: (1, 1),
+                MATHV_CLAMP100_WV: (6, 6)}   # (input planes, output planes)
 RACE_COMPARE, RACE_COMPETE = 0, 1
 POLICY_TANH, POLICY_RELU = 0, 1
 POLICY_RAW, POLICY_RELATIVE, POLICY_ABSOLUTE = 0, 1, 2

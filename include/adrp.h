@@ -494,6 +494,26 @@ int adrp_set_noise(adrp_t* h, const double* act_noise_dev, const double* force_d
 #define ADRP_MATH_FDIV_RCP 23      /* float(in[i]) / float(in[n + i]) as the fp64 race firmware divides (f64::fdiv_rcp) */
 int adrp_math_probe(int fn, const double* in_dev, double* out_dev, int n, void* stream);
 
+/* The vector form: the attitude conversions and the fp32 fast forms of csrc/adrp_device.h, evaluated in
+ * float (precision 0) or double (precision 1) on planes in_dev[k_in][n] -> out_dev[k_out][n] of device
+ * doubles (a float evaluation rounds its inputs to float and widens its results).  Column i runs in lane
+ * i % 64 of wave i / 64, so the caller decides which columns share a wave-uniform vote.  Quaternions are
+ * xyzw, angles roll, pitch, yaw.  adrp_math_probe_v_planes reports k_in / k_out of a form. */
+#define ADRP_MATHV_EULER_XYZ 0            /* q[4] -> rpy[3]: libm atan2 / asin (the DSLPID controller input) */
+#define ADRP_MATHV_EULER_XYZ_FAST 1       /* q[4] -> rpy[3]: fatan2_ / fasin_, per-lane gimbal branches */
+#define ADRP_MATHV_EULER_XYZ_FAST_U 2     /* q[4] -> rpy[3]: the same behind the wave-uniform gimbal vote */
+#define ADRP_MATHV_QUAT_FROM_EULER 3      /* rpy[3] -> q[4]: libm sincos */
+#define ADRP_MATHV_QUAT_FROM_EULER_FAST 4 /* rpy[3] -> q[4]: the small series when all half angles <= pi/8 */
+#define ADRP_MATHV_FATAN2 5               /* (y, x) -> fatan2_(y, x) */
+#define ADRP_MATHV_FASIN 6                /* s -> fasin_(s), |s| < 1 */
+#define ADRP_MATHV_FEXP 7                 /* x -> fexp_(x), x <= 0 in the kernels */
+#define ADRP_MATHV_SMALL_SINCOS 8         /* x -> (sin x, cos x), |x| <= pi/8 */
+#define ADRP_MATHV_EXPMAP_SINC_COS 9      /* x -> (sin(x) / x, cos x), |x| <= pi/8 */
+#define ADRP_MATHV_QUAT_INV_NORM 10       /* n2 -> 1 / sqrt(n2) */
+#define ADRP_MATHV_CLAMP100_WV 11         /* (w[3], v[3]) -> the same clamped to [-100, 100] (clamp100_wv) */
+int adrp_math_probe_v_planes(int fn, int* k_in, int* k_out);
+int adrp_math_probe_v(int fn, int precision, const double* in_dev, double* out_dev, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

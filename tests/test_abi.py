@@ -132,3 +132,18 @@ def test_pid_action_kernels(lib):
     c = cfg.copy()
     c.act_type = 6
     assert _lib.kernel_name(c).startswith("hover_step<")   # naming only; adrp_create rejects it
+
+
+def test_math_probe_v_planes_mirrored(lib):
+    """adrp_math_probe_v: the Python mirror of every form's input / output plane count is the library's,
+    and ids outside the table are refused"""
+    for fn, planes in abi.MATHV_PLANES.items():
+        a, b = ctypes.c_int(), ctypes.c_int()
+        assert lib.adrp_math_probe_v_planes(fn, ctypes.byref(a), ctypes.byref(b)) == 0
+        assert (a.value, b.value) == planes
+    assert sorted(abi.MATHV_PLANES) == list(range(len(abi.MATHV_PLANES)))
+    for fn in (-1, len(abi.MATHV_PLANES)):
+        assert lib.adrp_math_probe_v_planes(fn, None, None) == abi.ERR_INVALID
+        assert lib.adrp_math_probe_v(fn, 0, None, None, 0, None) == abi.ERR_INVALID
+    assert lib.adrp_math_probe_v(abi.MATHV_FATAN2, 2, None, None, 0, None) == abi.ERR_INVALID
+    assert lib.adrp_math_probe_v(abi.MATHV_FATAN2, 0, None, None, 0, None) == 0     # n = 0: nothing launched
