@@ -108,6 +108,22 @@ def load():
     lib.adrp_policy_sample.restype = I
     lib.adrp_gae.argtypes = [P, P, P, P, P, I, I, ctypes.c_double, ctypes.c_double, P, P, P]
     lib.adrp_gae.restype = I
+    lib.adrp_ppo_default_cfg.argtypes = [P]
+    lib.adrp_ppo_default_cfg.restype = I
+    lib.adrp_ppo_create.argtypes = [P, P, ctypes.POINTER(P)]
+    lib.adrp_ppo_create.restype = I
+    lib.adrp_ppo_update.argtypes = [P, P, I, P, P, P, P, P, P, I, P, P]
+    lib.adrp_ppo_update.restype = I
+    lib.adrp_ppo_param_count.argtypes = [P]
+    lib.adrp_ppo_param_count.restype = I
+    lib.adrp_ppo_params.argtypes = [P, P, P, P, P, P]
+    lib.adrp_ppo_params.restype = I
+    lib.adrp_ppo_set_params.argtypes = [P, P, P, P, I, P]
+    lib.adrp_ppo_set_params.restype = I
+    lib.adrp_ppo_gradients.argtypes = [P, P, P]
+    lib.adrp_ppo_gradients.restype = I
+    lib.adrp_ppo_destroy.argtypes = [P]
+    lib.adrp_ppo_destroy.restype = None
     lib.adrp_compact_rows.argtypes = [P, P, P, I, I, I, P, P, P, P]
     lib.adrp_compact_rows.restype = I
     lib.adrp_memcpy_async.argtypes = [P, P, ctypes.c_size_t, I, P]

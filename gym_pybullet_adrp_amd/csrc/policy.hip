@@ -13,23 +13,12 @@
 
 #include "../../include/adrp.h"
 #include "policy_kernel.h"
+#include "policy_handle.h"
 #include "device_guard.h"
 
 using namespace adrp;
 
 int seterr(adrp_t* h, int code, const std::string& msg);
-
-struct adrp_policy {
-    int device = 0;
-    int in_dim = 0, h1 = 0, h2 = 0, relu = 0, act_dim = 4;
-    int row_tiles = 0;       // 16-row tiles per block (ADRP_POLICY_RT; 0 = default)
-    int wide = 0;            // served by the wide kernels: in_dim > 64, act_dim > 4 or ADRP_POLICY_WIDE=1
-    PolicyLayout L{};
-    float* blob = nullptr;   // device fragment blob
-    PolicyLayout Lc{};       // critic (adrp_policy_set_critic)
-    float* critic = nullptr;
-    float* log_std = nullptr;
-};
 
 // Pre-permute the Linear weights (torch layout [out][in], row-major) into the per-lane MFMA
 // fragments policy_kernel reads (see policy_kernel.h for the k order).  wide: layer 1 holds

@@ -1,0 +1,174 @@
+"""On-device PPO update (the learner half of examples/learn.py:72-94, ``model.learn``).
+
+``PPOLearner`` is stable_baselines3 2.3.2 ``PPO.train()`` for the ``MlpPolicy`` a ``DevicePolicy``
+serves (actor, separate critic, state-independent ``log_std``), restated from SB3's published code:
+per minibatch the clipped-surrogate loss, its gradient with respect to the 13 parameter tensors,
+``clip_grad_norm_`` and ``torch.optim.Adam(eps=1e-5)``, in four HIP launches on the tensors a
+``RolloutCollector`` already holds (csrc/ppo_kernel.h).  Each update rewrites the attached policy's
+device weights in place, so the next ``collect()`` samples from the updated policy; nothing
+synchronises with the host.  ``target_kl`` early stopping (a host read per minibatch) and
+learning-rate / clip-range schedules are not implemented.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .policy import ACTOR_KEYS, CRITIC_KEYS
+from .utils import abi
+
+KEYS = ACTOR_KEYS + CRITIC_KEYS
+STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+
+
+class PPOLearner:
+    """SB3 ``PPO.train()`` on the device for ``policy`` (a ``DevicePolicy`` with a critic).  The
+    learner must be closed (or dropped) before its policy, and the policy's ``set_critic`` must not
+    be called while a learner is attached."""
+
+    def __init__(self, policy, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, clip_range_vf=None,
+                 normalize_advantage=True, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=0, target_kl=None):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.AdrpError("no HIP device visible: libadrp has no CPU fallback")
+        if target_kl is not None:
+            raise ValueError("target_kl early stopping needs a host read per minibatch and is not implemented")
+        if int(n_epochs) < 1 or int(batch_size) < 1:
+            raise ValueError("n_epochs and batch_size must be at least 1")
+        self.policy = policy
+        self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
+        cfg = abi.AdrpPpoCfg()
+        self.lib.adrp_ppo_default_cfg(ctypes.byref(cfg))
+        cfg.learning_rate, cfg.clip_range = float(learning_rate), float(clip_range)
+        cfg.clip_range_vf = -1.0 if clip_range_vf is None else float(clip_range_vf)
+        cfg.normalize_advantage = int(bool(normalize_advantage))
+        cfg.ent_coef, cfg.vf_coef, cfg.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
+        if clip_range_vf is not None and cfg.clip_range_vf < 0:
+            raise ValueError("clip_range_vf must not be negative")
+        h = ctypes.c_void_p()
+        rc = self.lib.adrp_ppo_create(getattr(policy, "h", None), ctypes.byref(cfg), ctypes.byref(h))
+        if rc != 0:
+            msg = self.lib.adrp_last_error(None).decode()
+            raise (ValueError if rc == abi.ERR_INVALID else _lib.AdrpError)(msg)
+        self.h, self.cfg = h, cfg
+        self.device = policy.device
+        self.total = self.lib.adrp_ppo_param_count(h)
+        A, D, H1, H2 = policy.act_dim, policy.in_dim, policy.h1, policy.h2
+        net = lambda out: [(H1, D), (H1,), (H2, H1), (H2,), (out, H2), (out,)]
+        self.shapes = dict(zip(KEYS, net(A) + net(1) + [(A,)]))
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+        self._stats = torch.zeros(5, dtype=torch.float32, device=self.device)
+
+    # ---- flat vector <-> {SB3 key: tensor} ----
+    def _split(self, flat):
+        out, o = {}, 0
+        for k in KEYS:
+            n = 1
+            for s in self.shapes[k]:
+                n *= s
+            out[k] = flat[o:o + n].view(self.shapes[k])
+            o += n
+        assert o == self.total
+        return out
+
+    def _join(self, sd):
+        return torch.cat([torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32).reshape(-1) for k in KEYS])
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self.lib.adrp_last_error(None).decode()
+            raise (ValueError if rc == abi.ERR_INVALID else _lib.AdrpError)(f"{what}: {msg}")
+
+    def _flat(self):
+        return torch.empty(self.total, dtype=torch.float32, device=self.device)
+
+    def _stream(self):
+        return _lib._raw_stream(self.device.index)
+
+    def state_dict(self):
+        """the 13 tensors under SB3's key names (device copies): ``torch.save`` of it is a policy.pth,
+        ``DevicePolicy(sd_on_cpu, ...)`` rebuilds the same policy"""
+        p = self._flat()
+        self._check(self.lib.adrp_ppo_params(self.h, p.data_ptr(), None, None, None, self._stream()), "adrp_ppo_params")
+        return self._split(p)
+
+    def load_state_dict(self, sd):
+        p = self._join(sd)
+        self._check(self.lib.adrp_ppo_set_params(self.h, p.data_ptr(), None, None, -1, self._stream()), "adrp_ppo_set_params")
+        torch.cuda.current_stream(self.device).synchronize()      # p may be freed after the call
+
+    def optimizer_state_dict(self):
+        """Adam's state: {"exp_avg": {key: tensor}, "exp_avg_sq": {key: tensor}, "step": int}"""
+        m, v = self._flat(), self._flat()
+        t = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._check(self.lib.adrp_ppo_params(self.h, None, m.data_ptr(), v.data_ptr(), t.data_ptr(), self._stream()),
+                    "adrp_ppo_params")
+        return {"exp_avg": self._split(m), "exp_avg_sq": self._split(v), "step": int(t.item())}
+
+    def load_optimizer_state_dict(self, osd):
+        m, v = self._join(osd["exp_avg"]), self._join(osd["exp_avg_sq"])
+        self._check(self.lib.adrp_ppo_set_params(self.h, None, m.data_ptr(), v.data_ptr(), int(osd["step"]), self._stream()),
+                    "adrp_ppo_set_params")
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def gradients(self):
+        """{SB3 key: tensor}: the raw (pre-clip) gradients of the last update"""
+        gflat = self._flat()
+        self._check(self.lib.adrp_ppo_gradients(self.h, gflat.data_ptr(), self._stream()), "adrp_ppo_gradients")
+        return self._split(gflat)
+
+    def update(self, obs, actions, old_values, old_log_prob, advantages, returns, idx, stats=None):
+        """one minibatch: rows ``idx`` (int64 device tensor) of the flattened buffers obs [R, D],
+        actions [R, A], old_values / old_log_prob / advantages / returns [R] -> stats [5] (device:
+        policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction)"""
+        R = obs.shape[0]
+        for t, n in ((obs, None), (actions, R * self.policy.act_dim), (old_values, R), (old_log_prob, R), (advantages, R),
+                     (returns, R)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (n is None or t.numel() == n)):
+                raise ValueError("the buffers must be contiguous float32 device tensors of matching row count")
+        if obs.dim() != 2 or obs.shape[1] < self.policy.in_dim:
+            raise ValueError("obs must be [rows, D] with D >= the policy's in_dim")
+        if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 1):
+            raise ValueError("idx must be a contiguous int64 device tensor")
+        stats = self._stats if stats is None else stats
+        assert stats.is_cuda and stats.dtype == torch.float32 and stats.numel() == 5 and stats.is_contiguous()
+        rc = self.lib.adrp_ppo_update(self.h, obs.data_ptr(), obs.shape[1], actions.data_ptr(), old_values.data_ptr(),
+                                      old_log_prob.data_ptr(), advantages.data_ptr(), returns.data_ptr(), idx.data_ptr(),
+                                      idx.numel(), stats.data_ptr(), self._stream())
+        self._check(rc, "adrp_ppo_update")
+        return stats
+
+    def train(self, col, permutations=None, target_kl=None):
+        """``n_epochs`` passes over the collector's T x E samples, each a fresh random permutation cut
+        into consecutive slices of ``batch_size`` (the last one shorter), as RolloutBuffer.get yields
+        them.  ``permutations``: int64 [n_epochs, T E] to use instead of ``torch.randperm``.  Returns
+        the statistics [n_epochs, n_minibatches, 5] (device tensor; nothing is read back)."""
+        if target_kl is not None:
+            raise ValueError("target_kl early stopping needs a host read per minibatch and is not implemented")
+        n = col.T * col.E
+        flat = (col.obs.view(n, -1), col.actions.view(n, -1), col.values.view(n), col.log_probs.view(n),
+                col.advantages.view(n), col.returns.view(n))
+        if permutations is not None:
+            permutations = permutations.to(device=self.device, dtype=torch.int64).contiguous()
+            if tuple(permutations.shape) != (self.n_epochs, n):
+                raise ValueError(f"permutations must be [n_epochs, {n}]")
+        nmb = (n + self.batch_size - 1) // self.batch_size
+        stats = torch.zeros((self.n_epochs, nmb, 5), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            for e in range(self.n_epochs):
+                perm = permutations[e] if permutations is not None else torch.randperm(n, device=self.device, generator=self._gen)
+                for k, s in enumerate(range(0, n, self.batch_size)):
+                    self.update(*flat, perm[s:s + self.batch_size], stats=stats[e, k])
+        return stats
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.adrp_ppo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -138,3 +138,10 @@ class AdrpVecIO(ctypes.Structure):
     _fields_ = [("act", _p), ("obs", _p), ("rew", _p), ("term", _p), ("trunc", _p), ("done", _p),
                 ("count", _p), ("idx", _p), ("rows", _p), ("cap", ctypes.c_int),
                 ("term_dev", _p), ("trunc_dev", _p), ("tobs_dev", _p), ("idx_dev", _p)]
+
+
+class AdrpPpoCfg(ctypes.Structure):
+    """adrp_ppo_cfg (include/adrp.h): the constants of PPOLearner's minibatch update"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("normalize_advantage", _i32),
+                ("learning_rate", _d), ("clip_range", _d), ("clip_range_vf", _d),
+                ("ent_coef", _d), ("vf_coef", _d), ("max_grad_norm", _d)]

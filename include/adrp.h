@@ -402,6 +402,55 @@ int adrp_gae(const float* rewards, const float* values, const float* episode_sta
              const float* dones, int n_steps, int n_envs, double gamma, double gae_lambda, float* advantages,
              float* returns, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * On-device PPO update (examples/learn.py:72-94: model.learn -> PPO.train): the clipped-surrogate
+ * minibatch update of stable_baselines3 2.3.2 PPO.train() for the MlpPolicy above, restated from
+ * SB3's published code (not pinned against an SB3 run): evaluate_actions at the stored, unclipped
+ * actions, advantage normalisation (unbiased std, + 1e-8, n > 1), policy / value / entropy loss,
+ * the gradient with respect to the 13 tensors (mlp_extractor.policy_net.{0,2}, action_net,
+ * mlp_extractor.value_net.{0,2}, value_net, log_std), clip_grad_norm_ over all of them and
+ * torch.optim.Adam (betas 0.9 / 0.999, eps 1e-5, no weight decay).  csrc/ppo_kernel.h.
+ *
+ * A learner is attached to a policy with a critic and takes its initial parameters from the
+ * policy's device blobs.  Every update rewrites the policy's actor blob, critic blob and log_std in
+ * place (the pointers never change: adrp_policy_act / adrp_policy_sample launched afterwards on
+ * the same stream see the new weights, a captured graph stays valid).  Lifetime: destroy the learner
+ * before its policy, and do not call adrp_policy_set_critic on a policy that has a learner.
+ *
+ * adrp_ppo_update: one minibatch of n rows idx[0..n) (int64, device) of the flattened rollout buffers
+ * obs [rows][obs_stride], actions [rows][act_dim], old_values / old_log_prob / advantages / returns
+ * [rows] (float32, device).  Four launches on `stream` (three without advantage normalisation), no host
+ * synchronisation, capturable; Adam's step count lives on the device.  stats_out (device, 5 floats or NULL): policy_loss, value_loss,
+ * entropy_loss, approx_kl, clip_fraction.  Results are bitwise reproducible.
+ *
+ * The flat parameter vector: the 13 tensors in the order above (actor 6, critic 6, log_std), each in
+ * torch layout, adrp_ppo_param_count floats.  adrp_ppo_params copies parameters, Adam's m and v
+ * (device, that many floats each) and t (device, one int32) out, any of them NULL to skip;
+ * adrp_ppo_set_params copies them in (t < 0 keeps the step count) and re-packs the policy;
+ * adrp_ppo_gradients copies the last update's raw (pre-clip) gradient out.
+ * --------------------------------------------------------------------------------------- */
+typedef struct adrp_ppo adrp_ppo_t;
+typedef struct adrp_ppo_cfg {
+    uint32_t struct_size;        /* sizeof(adrp_ppo_cfg) */
+    int32_t normalize_advantage;
+    double learning_rate;        /* > 0 */
+    double clip_range;           /* >= 0 */
+    double clip_range_vf;        /* < 0: none (SB3's default None) */
+    double ent_coef;
+    double vf_coef;
+    double max_grad_norm;
+} adrp_ppo_cfg;
+int adrp_ppo_default_cfg(adrp_ppo_cfg* cfg);      /* SB3's defaults: 3e-4, 0.2, none, 0.0, 0.5, 0.5, normalise */
+int adrp_ppo_create(adrp_policy_t* policy, const adrp_ppo_cfg* cfg, adrp_ppo_t** out);
+int adrp_ppo_update(adrp_ppo_t* ppo, const float* obs, int obs_stride, const float* actions, const float* old_values,
+                    const float* old_log_prob, const float* advantages, const float* returns, const int64_t* idx,
+                    int n, float* stats_out, void* stream);
+int adrp_ppo_param_count(const adrp_ppo_t* ppo);
+int adrp_ppo_params(adrp_ppo_t* ppo, float* params_out, float* m_out, float* v_out, int32_t* t_out, void* stream);
+int adrp_ppo_set_params(adrp_ppo_t* ppo, const float* params, const float* m, const float* v, int t, void* stream);
+int adrp_ppo_gradients(adrp_ppo_t* ppo, float* grad_out, void* stream);
+void adrp_ppo_destroy(adrp_ppo_t* ppo);
+
 /* SB3 VecEnv host path: the terminal observations of the finished envs, compacted on the device
  * behind the step's packed outputs so ONE device -> host copy returns them (replaces the per-env
  * infos[e]["terminal_observation"] = obs that stable_baselines3 DummyVecEnv.step_wait fills from
