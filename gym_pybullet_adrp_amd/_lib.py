@@ -48,6 +48,8 @@ def load():
     lib.adrp_reset.restype = I
     lib.adrp_step.argtypes = [P, P, P, P, P, P, P, P]
     lib.adrp_step.restype = I
+    lib.adrp_step_rpm.argtypes = [P, P, P, P, P, P, P]
+    lib.adrp_step_rpm.restype = I
     lib.adrp_state_layout.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
     lib.adrp_state_field.argtypes = [P, I, I]
     lib.adrp_state_field.restype = ctypes.c_char_p
@@ -236,6 +238,13 @@ class Handle:
         rc = self._step(self.h, act_ptr, *self._outs, _raw_stream(self._dev_index))
         if rc != 0:
             self._check(rc, "adrp_step")
+
+    def step_rpm_ptr(self, rpm_ptr):
+        """adrp_step_rpm (CtrlAviary) on the buffers of the last bind(): motor speeds in the handle's
+        own precision"""
+        rc = self.lib.adrp_step_rpm(self.h, rpm_ptr, *self._outs[:4], _raw_stream(self._dev_index))
+        if rc != 0:
+            self._check(rc, "adrp_step_rpm")
 
     def step(self, act, obs, rew, term, trunc, tobs=None):
         """act None: command mode, the setpoints the last command() left"""

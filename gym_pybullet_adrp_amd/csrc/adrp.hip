@@ -35,7 +35,8 @@ extern "C" const char* adrp_last_error(const adrp_t* h) { return h ? h->err.c_st
 // defaults (reference constructors; cf2x_IROS.urdf constants; level0.yaml track)
 // ---------------------------------------------------------------------------------------------
 extern "C" int adrp_default_config(int task, adrp_config* c) {
-    if (!c || (task != ADRP_TASK_HOVER && task != ADRP_TASK_RACE && task != ADRP_TASK_MULTIHOVER)) return seterr(nullptr, ADRP_ERR_INVALID, "task");
+    if (!c || (task != ADRP_TASK_HOVER && task != ADRP_TASK_RACE && task != ADRP_TASK_MULTIHOVER && !is_ctrl_task(task)))
+        return seterr(nullptr, ADRP_ERR_INVALID, "task");
     memset(c, 0, sizeof *c);
     c->struct_size = sizeof(adrp_config);
     c->task = task;
@@ -54,7 +55,7 @@ extern "C" int adrp_default_config(int task, adrp_config* c) {
     d.dw_coeff[0] = 2267.18; d.dw_coeff[1] = 0.16; d.dw_coeff[2] = -0.11;
     const double pp[4][2] = {{0.028, 0.028}, {-0.028, 0.028}, {-0.028, -0.028}, {0.028, -0.028}};
     for (int i = 0; i < 4; ++i) { d.prop_pos[i][0] = pp[i][0]; d.prop_pos[i][1] = pp[i][1]; }
-    if (task == ADRP_TASK_HOVER || task == ADRP_TASK_MULTIHOVER) {
+    if (task == ADRP_TASK_HOVER || task == ADRP_TASK_MULTIHOVER || is_ctrl_task(task)) {
         c->act_type = ADRP_ACT_RPM;
         c->num_drones = 1;
         c->pyb_freq = 240; c->ctrl_freq = 30;                // HoverAviary.py:18-19
@@ -65,6 +66,16 @@ extern "C" int adrp_default_config(int task, adrp_config* c) {
         if (task == ADRP_TASK_MULTIHOVER) {                  // MultiHoverAviary.py:17 num_drones = 2
             c->num_drones = 2;
             for (int n = 0; n < c->num_drones; ++n) {        // BaseAviary.py:194-197
+                c->init_xyz[n][0] = 4 * d.l * n; c->init_xyz[n][1] = 4 * d.l * n;
+                c->init_xyz[n][2] = d.collision_h / 2 - d.collision_z_offset + 0.1;
+            }
+        }
+        if (is_ctrl_task(task)) {                            // CtrlAviary.py:16-20, VelocityAviary.py:16-22
+            c->act_type = task == ADRP_TASK_CTRL ? ADRP_ACT_RAW_RPM : ADRP_ACT_VEL;
+            c->pyb_freq = 240; c->ctrl_freq = 240;
+            // one drone; the rows of all eight are filled, so that raising num_drones alone gives the
+            // reference's default formation (BaseAviary.py:194-197)
+            for (int n = 0; n < ADRP_MAX_DRONES; ++n) {
                 c->init_xyz[n][0] = 4 * d.l * n; c->init_xyz[n][1] = 4 * d.l * n;
                 c->init_xyz[n][2] = d.collision_h / 2 - d.collision_z_offset + 0.1;
             }
@@ -194,10 +205,7 @@ static int upload_const(adrp_t* h) {
 
 // MultiHoverAviary: [HoverConst | HoverReset | MultiConst] (multihover_const)
 template <typename Real>
-static int upload_multihover_const(adrp_t* h) {
-    const adrp_config& c = h->cfg;
-    const HoverConst<Real> k = hover_const<Real>(c);
-    const HoverReset<Real> r = hover_reset_dist<Real>(c);
+static MultiConst<Real> multi_const(const adrp_config& c) {
     MultiConst<Real> m;
     memset(&m, 0, sizeof m);
     m.N = c.num_drones;
@@ -210,6 +218,14 @@ static int upload_multihover_const(adrp_t* h) {
             // TARGET_POS = INIT_XYZS + [0, 0, 1/(i+1)] in float64 (MultiHoverAviary.py:71)
             m.target[n][j] = Real(c.init_xyz[n][j] + (j == 2 ? 1.0 / (n + 1) : 0.0));
         }
+    return m;
+}
+
+// X: MultiConst (MultiHoverAviary) or CtrlConst (CtrlAviary / VelocityAviary)
+template <typename Real, typename X>
+static int upload_multi_block(adrp_t* h, const X& m) {
+    const HoverConst<Real> k = hover_const<Real>(h->cfg);
+    const HoverReset<Real> r = hover_reset_dist<Real>(h->cfg);
     const size_t off = multihover_const_offset<Real>();
     if (hipMalloc(&h->cblk, off + sizeof m) != hipSuccess) return ADRP_ERR_OOM;
     if (hipMemcpy(h->cblk, &k, sizeof k, hipMemcpyHostToDevice) != hipSuccess ||
@@ -217,6 +233,25 @@ static int upload_multihover_const(adrp_t* h) {
         hipMemcpy((char*)h->cblk + off, &m, sizeof m, hipMemcpyHostToDevice) != hipSuccess)
         return ADRP_ERR_DEVICE;
     return ADRP_OK;
+}
+
+template <typename Real>
+static int upload_multihover_const(adrp_t* h) {
+    return upload_multi_block<Real>(h, multi_const<Real>(h->cfg));
+}
+
+static double max_rpm(const adrp_config& c) {   // BaseAviary.py:120
+    const double gravity = c.gravity * c.drone.m;   // GRAVITY = G M first, as the reference rounds it
+    return sqrt((c.drone.thrust2weight * gravity) / (4 * c.drone.kf));
+}
+
+template <typename Real>
+static int upload_ctrl_const(adrp_t* h) {
+    CtrlConst<Real> k;
+    memset(&k, 0, sizeof k);
+    k.m = multi_const<Real>(h->cfg);
+    k.max_rpm = Real(max_rpm(h->cfg));
+    return upload_multi_block<Real>(h, k);
 }
 
 template <typename Real>
@@ -355,6 +390,11 @@ extern "C" const char* adrp_kernel_name(const adrp_config* cfg) {
                  race_group(cfg->num_drones), quad ? ",Q4" : "");
         return buf;
     }
+    if (is_ctrl_task(cfg->task)) {
+        snprintf(buf, sizeof buf, "%s_step<%s,%s,G%d>", cfg->task == ADRP_TASK_CTRL ? "ctrl" : "velocity",
+                 cfg->precision ? "f64" : "f32", ph[p], mh_group(cfg->num_drones));
+        return buf;
+    }
     const int A = hover_act_dim(cfg->act_type);
     if (cfg->task == ADRP_TASK_MULTIHOVER) {
         snprintf(buf, sizeof buf, "multihover_step<%s,%s,A%d,G%d>", cfg->precision ? "f64" : "f32", ph[p], A,
@@ -422,6 +462,14 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
             return seterr(nullptr, ADRP_ERR_INVALID, "MultiHoverAviary act_type must be RPM or ONE_D_RPM");
         if (c.action_buffer_size <= 0 || c.action_buffer_size > 4096)
             return seterr(nullptr, ADRP_ERR_INVALID, "action_buffer_size");
+    } else if (c.task == ADRP_TASK_CTRL) {
+        if (c.num_drones < 1 || c.num_drones > ADRP_MAX_DRONES)
+            return seterr(nullptr, ADRP_ERR_INVALID, "CtrlAviary num_drones must be 1..8");
+        if (c.act_type != ADRP_ACT_RAW_RPM) return seterr(nullptr, ADRP_ERR_INVALID, "CtrlAviary act_type must be RAW_RPM");
+    } else if (c.task == ADRP_TASK_VELOCITY) {
+        if (c.num_drones < 1 || c.num_drones > ADRP_MAX_DRONES)
+            return seterr(nullptr, ADRP_ERR_INVALID, "VelocityAviary num_drones must be 1..8");
+        if (c.act_type != ADRP_ACT_VEL) return seterr(nullptr, ADRP_ERR_INVALID, "VelocityAviary act_type must be VEL");
     } else if (c.task == ADRP_TASK_RACE) {
         if (c.num_drones < 1 || c.num_drones > ADRP_MAX_DRONES)
             return seterr(nullptr, ADRP_ERR_INVALID, "MultiRaceAviary num_drones must be 1..8");
@@ -444,9 +492,11 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
     h->device = device;
     h->E = c.num_envs; h->N = c.num_drones;
     const bool race = c.task == ADRP_TASK_RACE;
-    h->A = race ? 4 : hover_act_dim(c.act_type);
-    h->B = race ? 0 : c.action_buffer_size;
-    h->D = race ? 49 + (c.race_mode == ADRP_RACE_COMPETE ? 6 * (c.num_drones - 1) : 0) : 12 + h->B * h->A;
+    const bool ctrl = is_ctrl_task(c.task);   // no action history: no ring, action_buffer_size is not read
+    h->A = race || ctrl ? 4 : hover_act_dim(c.act_type);
+    h->B = race || ctrl ? 0 : c.action_buffer_size;
+    h->D = race ? 49 + (c.race_mode == ADRP_RACE_COMPETE ? 6 * (c.num_drones - 1) : 0)
+                : ctrl ? kCtrlObs : 12 + h->B * h->A;
     h->S = c.pyb_freq / c.ctrl_freq;
     h->nf_base = race ? RF_N : HF_NBASE + (hover_has_pid(c.act_type) ? HF_NPID : 0);
     h->ni = race ? RI_N : HI_N;
@@ -480,6 +530,7 @@ extern "C" int adrp_create(const adrp_config* cfg, int device, adrp_t** out) {
     const int rc = race ? (h->real_size == 8 ? upload_race_const<double>(h) : upload_race_const<float>(h))
                    : c.task == ADRP_TASK_MULTIHOVER
                         ? (h->real_size == 8 ? upload_multihover_const<double>(h) : upload_multihover_const<float>(h))
+                   : ctrl ? (h->real_size == 8 ? upload_ctrl_const<double>(h) : upload_ctrl_const<float>(h))
                         : (h->real_size == 8 ? upload_const<double>(h) : upload_const<float>(h));
     if (rc != ADRP_OK) return cleanup(seterr(h, rc, "constant block upload failed"));
     if (const char* env = getenv("ADRP_RESET_IMAGES")) h->img_period = atoi(env);
@@ -572,6 +623,9 @@ extern "C" int adrp_reset(adrp_t* h, const uint8_t* env_mask_dev, float* obs_dev
     if (h->cfg.task == ADRP_TASK_MULTIHOVER)
         return h->real_size == 8 ? multihover_reset<double>(h, env_mask_dev, obs_dev, s)
                                  : multihover_reset<float>(h, env_mask_dev, obs_dev, s);
+    if (is_ctrl_task(h->cfg.task))
+        return h->real_size == 8 ? ctrl_reset<double>(h, env_mask_dev, obs_dev, s)
+                                 : ctrl_reset<float>(h, env_mask_dev, obs_dev, s);
     return h->real_size == 8 ? hover_reset<double>(h, env_mask_dev, obs_dev, s)
                              : hover_reset<float>(h, env_mask_dev, obs_dev, s);
 }
@@ -589,8 +643,22 @@ extern "C" int adrp_step(adrp_t* h, const float* act_dev, float* obs_dev, float*
     if (h->cfg.task == ADRP_TASK_MULTIHOVER)
         return h->real_size == 8 ? multihover_step<double>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s)
                                  : multihover_step<float>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s);
+    if (is_ctrl_task(h->cfg.task))   // (no episode ends: terminal_obs_dev is never written)
+        return h->real_size == 8 ? ctrl_step<double>(h, act_dev, nullptr, obs_dev, rew_dev, term_dev, trunc_dev, s)
+                                 : ctrl_step<float>(h, act_dev, nullptr, obs_dev, rew_dev, term_dev, trunc_dev, s);
     return h->real_size == 8 ? hover_step<double>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s)
                              : hover_step<float>(h, act_dev, obs_dev, rew_dev, term_dev, trunc_dev, terminal_obs_dev, s);
+}
+
+extern "C" int adrp_step_rpm(adrp_t* h, const void* rpm_dev, float* obs_dev, float* rew_dev, uint8_t* term_dev,
+                             uint8_t* trunc_dev, void* stream) {
+    if (!h || !rpm_dev || !obs_dev || !rew_dev || !term_dev || !trunc_dev)
+        return seterr(h, ADRP_ERR_INVALID, "adrp_step_rpm: NULL argument");
+    if (h->cfg.task != ADRP_TASK_CTRL) return seterr(h, ADRP_ERR_INVALID, "adrp_step_rpm: CtrlAviary handles only");
+    DeviceGuard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    return h->real_size == 8 ? ctrl_step<double>(h, nullptr, rpm_dev, obs_dev, rew_dev, term_dev, trunc_dev, s)
+                             : ctrl_step<float>(h, nullptr, rpm_dev, obs_dev, rew_dev, term_dev, trunc_dev, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -820,7 +888,7 @@ extern "C" int adrp_set_state(adrp_t* h, const void* f_dev, const int32_t* i_dev
     HIPCHK(h, hipGetLastError());
     (void)nr;
     HIPCHK(h, hipMemcpyAsync(h->ist, i_dev, h->ni * EN * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (h->cfg.task == ADRP_TASK_MULTIHOVER && h->N > 1) {   // the env's ints are drone 0's
+    if ((h->cfg.task == ADRP_TASK_MULTIHOVER || is_ctrl_task(h->cfg.task)) && h->N > 1) {   // the env's ints are drone 0's
         hipLaunchKernelGGL(spread_ints_kernel, dim3((h->E + 255) / 256), dim3(256), 0, s, h->ist, h->ni, h->E, h->N);
         HIPCHK(h, hipGetLastError());
     }
@@ -846,6 +914,13 @@ extern "C" int64_t adrp_step_bytes(const adrp_t* h) {
     const bool drag = ph == ADRP_PHYS_PYB_DRAG || ph == ADRP_PHYS_PYB_GND_DRAG_DW;
     const bool lag = h->cfg.link_frame_lag && !dyn;
     const int64_t fields = 13 + (lag ? 4 : 0) + (drag ? 4 : 0) + (dyn ? 3 : 0) + (h->nf_base - HF_NBASE);
+    if (is_ctrl_task(h->cfg.task)) {
+        // per drone: the state read and written (last_rpm read only by the drag modes, written by all),
+        // step_counter read + written, the action (float32, or the handle's precision through
+        // adrp_step_rpm: counted as float32), the 80-byte row; per env: reward + 2 flags
+        const int64_t per_drone = (2 * fields + (drag ? 0 : 4)) * int64_t(h->real_size) + 2 * 4 + 4 * 4 + kCtrlObs * 4;
+        return (per_drone * h->N + 6) * h->E;
+    }
     const int64_t per_env = 2 * fields * int64_t(h->real_size)   // state read + write
                             + 2 * HI_N * 4                        // int state read + write
                             + int64_t(h->A) * 4                   // action

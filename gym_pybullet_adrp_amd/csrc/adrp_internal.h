@@ -14,6 +14,7 @@
 #include "../../include/adrp.h"
 #include "hover_kernel.h"
 #include "multihover_kernel.h"
+#include "ctrl_kernel.h"
 #include "race_kernel.h"
 #include "race_quad.h"
 #include "device_guard.h"
@@ -131,6 +132,13 @@ inline const MultiConst<Real>* multihover_const(const adrp_t* h) {
     return (const MultiConst<Real>*)((const char*)h->cblk + multihover_const_offset<Real>());
 }
 
+// CtrlAviary / VelocityAviary: [HoverConst | HoverReset | CtrlConst] at the same offset
+template <typename Real>
+inline const CtrlConst<Real>* ctrl_const(const adrp_t* h) {
+    return (const CtrlConst<Real>*)((const char*)h->cblk + multihover_const_offset<Real>());
+}
+inline bool is_ctrl_task(int task) { return task == ADRP_TASK_CTRL || task == ADRP_TASK_VELOCITY; }
+
 template <typename Real>
 constexpr size_t race_ticks_offset() { return (sizeof(RaceConst<Real>) + 255) & ~size_t(255); }
 
@@ -171,6 +179,11 @@ int multihover_step(adrp_t* h, const float* act, float* obs, float* rew, uint8_t
                     hipStream_t s);
 template <typename Real>
 int multihover_reset(adrp_t* h, const uint8_t* mask, float* obs, hipStream_t s);
+template <typename Real>
+int ctrl_step(adrp_t* h, const float* act, const void* rpm_real, float* obs, float* rew, uint8_t* term, uint8_t* trunc,
+              hipStream_t s);
+template <typename Real>
+int ctrl_reset(adrp_t* h, const uint8_t* mask, float* obs, hipStream_t s);
 template <typename Real>
 int hover_persist_launch(adrp_t* h, const HoverArgs<Real>& a, void* ctl, hipStream_t s);
 template <typename Real>

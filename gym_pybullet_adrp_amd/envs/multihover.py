@@ -57,7 +57,66 @@ def multihover_spaces(num_drones, act=ActionType.RPM, action_buffer_size=15):
             Box(low=np.array([low] * num_drones), high=np.array([high] * num_drones), dtype=np.float32))
 
 
-class MultiHoverAviary(AviaryEnv):
+class MultiDroneHelpers:
+    """What the envs with N drones per env share (MultiHoverAviary, CtrlAviary, VelocityAviary): the
+    neighbourhood helpers and the introspection of the handle ``self.h``."""
+
+    # ---- multi-drone helpers (torch, from the state snapshot: no kernel of their own) ----
+    def close(self):
+        self.h.close()
+
+    def _positions(self):
+        """[E, N, 3] drone positions (state snapshot columns e*N + n)"""
+        if self._pos_rows is None:
+            names = self.state_field_names()[0]
+            self._pos_rows = [names.index(k) for k in ("pos_x", "pos_y", "pos_z")]
+        f, _ = self.get_state()
+        return f[self._pos_rows].reshape(3, self.num_envs, self.NUM_DRONES).permute(1, 2, 0)
+
+    def adjacency_matrix(self):
+        """BaseAviary._getAdjacencyMatrix per env: [E, N, N] of 0 / 1, adj[e, i, j] == 1 iff i == j or
+        |pos_i - pos_j| < NEIGHBOURHOOD_RADIUS"""
+        p = self._positions()
+        dist = (p[:, :, None, :] - p[:, None, :, :]).norm(dim=-1)
+        adj = (dist < self.NEIGHBOURHOOD_RADIUS).to(p.dtype)
+        eye = torch.eye(self.NUM_DRONES, dtype=p.dtype, device=p.device)
+        return torch.maximum(adj, eye.expand_as(adj))
+
+    def min_pair_distance(self):
+        """[E] the smallest centre distance between two drones of each env (inf for one drone).  Drone-drone
+        contact is not modelled: below about 2 * 0.06 m (the collision cylinders' radii) the reference's
+        Bullet would have resolved a contact that this env does not."""
+        p = self._positions()
+        N = self.NUM_DRONES
+        if N < 2:
+            return torch.full((self.num_envs,), float("inf"), dtype=p.dtype, device=p.device)
+        dist = (p[:, :, None, :] - p[:, None, :, :]).norm(dim=-1)
+        dist = dist + torch.diag(torch.full((N,), float("inf"), dtype=p.dtype, device=p.device))
+        return dist.reshape(self.num_envs, -1).min(dim=1).values
+
+    # ---- introspection (tests / teacher forcing) ----
+    def get_state(self):
+        """(float [nf, E*N], int32 [ni, E*N]): HoverAviary's fields, column e*N + n; the per-env ints
+        are replicated on the env's columns"""
+        return self.h.get_state()
+
+    def set_state(self, f, i):
+        """the per-env ints (step_counter, episode, ring_head) are taken from drone 0's column"""
+        self.h.set_state(f, i)
+
+    def state_field_names(self):
+        return self.h.field_names()
+
+    def step_bytes(self):
+        return self.h.step_bytes()
+
+    @property
+    def kernel_name(self):
+        """the step-kernel instantiation this env launches (include/adrp.h adrp_handle_kernel_name)"""
+        return self.h.kernel_name()
+
+
+class MultiHoverAviary(MultiDroneHelpers, AviaryEnv):
     """Batched counterpart of gym_pybullet_adrp.envs.MultiHoverAviary."""
 
     def __init__(self, drone_model: DroneModel = DroneModel.CF2X, num_drones: int = 2,
@@ -181,9 +240,6 @@ class MultiHoverAviary(AviaryEnv):
         self.h.step_ptr(act.data_ptr())
         return self._obs, self._rew, self._term, self._trunc, self._info
 
-    def close(self):
-        self.h.close()
-
     def bind_outputs(self, obs, rew, term, trunc, tobs=None):
         """Write step / reset outputs into caller-owned device tensors from now on: obs [E,N,D] float32,
         reward [E] float32, terminated / truncated [E] bool, optionally the terminal observations
@@ -199,54 +255,3 @@ class MultiHoverAviary(AviaryEnv):
             self._tobs = tobs
             self._info["terminal_observation"] = tobs
         self.h.bind(self._obs, self._rew, self._term, self._trunc, self._tobs)
-
-    # ---- multi-drone helpers (torch, from the state snapshot: no kernel of their own) ----
-    def _positions(self):
-        """[E, N, 3] drone positions (state snapshot columns e*N + n)"""
-        if self._pos_rows is None:
-            names = self.state_field_names()[0]
-            self._pos_rows = [names.index(k) for k in ("pos_x", "pos_y", "pos_z")]
-        f, _ = self.get_state()
-        return f[self._pos_rows].reshape(3, self.num_envs, self.NUM_DRONES).permute(1, 2, 0)
-
-    def adjacency_matrix(self):
-        """BaseAviary._getAdjacencyMatrix per env: [E, N, N] of 0 / 1, adj[e, i, j] == 1 iff i == j or
-        |pos_i - pos_j| < NEIGHBOURHOOD_RADIUS"""
-        p = self._positions()
-        dist = (p[:, :, None, :] - p[:, None, :, :]).norm(dim=-1)
-        adj = (dist < self.NEIGHBOURHOOD_RADIUS).to(p.dtype)
-        eye = torch.eye(self.NUM_DRONES, dtype=p.dtype, device=p.device)
-        return torch.maximum(adj, eye.expand_as(adj))
-
-    def min_pair_distance(self):
-        """[E] the smallest centre distance between two drones of each env (inf for one drone).  Drone-drone
-        contact is not modelled: below about 2 * 0.06 m (the collision cylinders' radii) the reference's
-        Bullet would have resolved a contact that this env does not."""
-        p = self._positions()
-        N = self.NUM_DRONES
-        if N < 2:
-            return torch.full((self.num_envs,), float("inf"), dtype=p.dtype, device=p.device)
-        dist = (p[:, :, None, :] - p[:, None, :, :]).norm(dim=-1)
-        dist = dist + torch.diag(torch.full((N,), float("inf"), dtype=p.dtype, device=p.device))
-        return dist.reshape(self.num_envs, -1).min(dim=1).values
-
-    # ---- introspection (tests / teacher forcing) ----
-    def get_state(self):
-        """(float [nf, E*N], int32 [ni, E*N]): HoverAviary's fields, column e*N + n; the per-env ints
-        are replicated on the env's columns"""
-        return self.h.get_state()
-
-    def set_state(self, f, i):
-        """the per-env ints (step_counter, episode, ring_head) are taken from drone 0's column"""
-        self.h.set_state(f, i)
-
-    def state_field_names(self):
-        return self.h.field_names()
-
-    def step_bytes(self):
-        return self.h.step_bytes()
-
-    @property
-    def kernel_name(self):
-        """the step-kernel instantiation this env launches (include/adrp.h adrp_handle_kernel_name)"""
-        return self.h.kernel_name()

@@ -12,9 +12,9 @@ MAX_OBSTACLES = 4
 
 OK, ERR_INVALID, ERR_DEVICE, ERR_OOM = 0, -1, -2, -3
 
-TASK_HOVER, TASK_RACE, TASK_MULTIHOVER = 0, 1, 2
+TASK_HOVER, TASK_RACE, TASK_MULTIHOVER, TASK_CTRL, TASK_VELOCITY = 0, 1, 2, 3, 4
 PHYS_PYB, PHYS_DYN, PHYS_PYB_GND, PHYS_PYB_DRAG, PHYS_PYB_DW, PHYS_PYB_GND_DRAG_DW = range(6)
-ACT_RPM, ACT_ONE_D_RPM, ACT_FULLSTATE, ACT_PID, ACT_VEL, ACT_ONE_D_PID = 0, 1, 2, 3, 4, 5
+ACT_RPM, ACT_ONE_D_RPM, ACT_FULLSTATE, ACT_PID, ACT_VEL, ACT_ONE_D_PID, ACT_RAW_RPM = 0, 1, 2, 3, 4, 5, 6
 MATH_RCP, MATH_RSQ, MATH_SQRT, MATH_SIN_SMALL, MATH_COS_SMALL, MATH_ATAN2, MATH_ASIN, MATH_EXP = range(8)   # adrp_math_probe
 MATH_SQRT_NN, MATH_RCP_NC, MATH_RSQ_NC, MATH_SIN_TINY, MATH_COS_TINY = 8, 9, 10, 11, 12
 MATH_EXPMAP_SINC, MATH_EXPMAP_COS, MATH_QUAT_INV_NORM, MATH_NORMAL_Z0, MATH_NORMAL_Z1 = 13, 14, 15, 16, 17

@@ -60,6 +60,20 @@ extern "C" {
  * Snapshot: HoverAviary's fields, [field][E*N], column e*N+n; the per-env ints (step_counter, episode,
  * ring_head) are replicated on the env's columns and adrp_set_state takes drone 0's. */
 #define ADRP_TASK_MULTIHOVER 2
+/* CtrlAviary (envs/CtrlAviary.py) and VelocityAviary (envs/VelocityAviary.py): the control-application
+ * envs, num_drones 1..8 per env.  The observation is the drone state row of _getDroneStateVector
+ * (BaseAviary.py:553-573), float [E,N,20] = pos 3, quat 4 (xyzw), rpy 3, vel 3, ang_v 3 and the four
+ * RPMs applied in this step (zero after a reset); the action is float [E,N,4]: motor speeds clipped to
+ * [0, MAX_RPM] (CTRL, act_type ADRP_ACT_RAW_RPM; adrp_step_rpm takes them in the handle's precision)
+ * or a velocity command (direction 3, fraction of SPEED_LIMIT 1) tracked by one DSLPIDControl per
+ * drone, called once per step before the sub-steps (VELOCITY, act_type ADRP_ACT_VEL).  reward -1,
+ * terminated / truncated 0, always: action_buffer_size and autoreset are ignored.  The downwash
+ * physics modes couple an env's drones as in MULTIHOVER.  Snapshot: HoverAviary's base fields without
+ * ring fields, [field][E*N], column e*N+n, last_rpm_* maintained in every physics mode; VELOCITY adds
+ * the nine pid_* fields, which adrp_reset leaves as they are (the reference builds its controllers
+ * once).  The ints are per column; adrp_set_state takes drone 0's for the env. */
+#define ADRP_TASK_CTRL 3
+#define ADRP_TASK_VELOCITY 4
 
 /* adrp_config.physics — utils/enums.py:18-26 (Physics) */
 #define ADRP_PHYS_PYB 0
@@ -77,6 +91,7 @@ extern "C" {
 #define ADRP_ACT_PID 3          /* a in R^3: waypoint, capped 1 m away (BaseRLAviary.py:193-207, BaseAviary.py:1112-1160) */
 #define ADRP_ACT_VEL 4          /* a in R^4: direction + |a3| x SPEED_LIMIT target velocity (BaseRLAviary.py:208-223) */
 #define ADRP_ACT_ONE_D_PID 5    /* a in R:   target z = z + 0.1a (BaseRLAviary.py:226-235) */
+#define ADRP_ACT_RAW_RPM 6      /* CtrlAviary: a in R^4, motor speeds, clipped to [0, MAX_RPM] (CtrlAviary.py:140) */
 
 /* adrp_config.race_mode — utils/enums.py:84-87 (RaceMode) */
 #define ADRP_RACE_COMPARE 0
@@ -200,7 +215,9 @@ int adrp_abi_version(void);
 
 /* Fill *cfg with the reference defaults for `task` (HoverAviary, MultiRaceAviary or MultiHoverAviary,
  * CF2X = cf2x_IROS.urdf constants, level0 track for RACE; MULTIHOVER: the hover default with two
- * drones at init_xyz[n] = (4Ln, 4Ln, COLLISION_H/2 - COLLISION_Z_OFFSET + 0.1), BaseAviary.py:194-197). */
+ * drones at init_xyz[n] = (4Ln, 4Ln, COLLISION_H/2 - COLLISION_Z_OFFSET + 0.1), BaseAviary.py:194-197;
+ * CTRL / VELOCITY: the hover default with one drone at 240 / 240 Hz (CtrlAviary.py:19-20,
+ * VelocityAviary.py:21-22), act_type RAW_RPM / VEL, and init_xyz[n] of that formula for all eight n). */
 int adrp_default_config(int task, adrp_config* cfg);
 
 /* Create a handle on GPU `device`; allocates all state in HBM. */
@@ -211,7 +228,7 @@ void adrp_destroy(adrp_t* h);
 const char* adrp_last_error(const adrp_t* h);
 
 /* Per-drone observation width D (12 + B*A for Hover: 72 RPM/VEL, 57 PID, 27 ONE_D_*;
- * 49 / 49+6(N-1) Race) and action width A (4, 3 or 1). */
+ * 49 / 49+6(N-1) Race; 20 CtrlAviary / VelocityAviary) and action width A (4, 3 or 1). */
 int adrp_obs_dim(const adrp_t* h);
 int adrp_act_dim(const adrp_t* h);
 
@@ -237,6 +254,13 @@ int adrp_reset(adrp_t* h, const uint8_t* env_mask_dev, float* obs_dev, void* str
  * the reset observation (SB3 VecEnv semantics). */
 int adrp_step(adrp_t* h, const float* act_dev, float* obs_dev, float* rew_dev,
               uint8_t* term_dev, uint8_t* trunc_dev, float* terminal_obs_dev, void* stream);
+
+/* ADRP_TASK_CTRL only: adrp_step with the motor speeds rpm_dev [E,N,4] in the handle's own precision
+ * (float32 for precision 0, float64 for precision 1).  The reference feeds float64 RPMs; rounding them
+ * to float32 first costs about 3e-5 relative in the velocity after one step, so a float64 handle that
+ * is to follow the reference to 1e-9 takes them here.  adrp_step with float32 RPMs stays valid. */
+int adrp_step_rpm(adrp_t* h, const void* rpm_dev, float* obs_dev, float* rew_dev,
+                  uint8_t* term_dev, uint8_t* trunc_dev, void* stream);
 
 /* MultiRaceAviary only: high-level command mode.  adrp_enable_commands
  * allocates the per-drone setpoint / commander / planner state; call it before the adrp_reset that
@@ -268,7 +292,8 @@ int adrp_set_state(adrp_t* h, const void* f_dev, const int32_t* i_dev, void* str
  * reference default drone at 240/30 Hz, chosen only when the config's derived constants
  * are bit-identical), "generic" = read from the handle's device-resident block.
  * MultiHoverAviary: "multihover_step<f32,PYB,A4,G2>", G = the lane-group width, the next power of two
- * >= num_drones (one lane per drone, a group per env). */
+ * >= num_drones (one lane per drone, a group per env).  CtrlAviary / VelocityAviary:
+ * "ctrl_step<f64,PYB_DW,G4>" / "velocity_step<f64,PYB_DW,G4>". */
 const char* adrp_kernel_name(const adrp_config* cfg);
 /* the instantiation this handle launches now (after adrp_enable_commands a race handle runs the
    command-mode kernel, "...,CMD>"; ADRP_RACE_QUAD as read at create) */

@@ -1,0 +1,570 @@
+"""CtrlAviary / VelocityAviary HIP kernels (one lane per (env, drone), csrc/ctrl_kernel.h).  Needs an MI355X: -m gpu.
+
+References are assembled from what exists: the reference's own CtrlAviary / VelocityAviary episodes
+(tests/golden/ctrl_golden.npz), the unchanged single-drone CPU oracle (tests/test_ctrl_reference.py pins it to
+those episodes), HoverAviary's kernel for N = 1 and MultiHoverAviary's for the downwash modes.
+
+Bars (tests/test_multihover_gpu.py): per state vector |x_gpu - x_ref| <= rtol * max(|x_ref|, floor), rtol 1e-9
+(fp64) / 1e-4 (fp32), the floors of FLOORS; the ints are exact.  Where both sides are float32 roundings of
+float64 values (obs rows against the fixture or the oracle's state), one float32 ulp (2^-23) is added.
+
+Shapes: N = 3 with E = 40 (G = 4: one dead lane per group, 160 lanes = two full waves and a partial one) and
+N = 5 with E = 9 (G = 8, three dead lanes per group, a partial second wave): the smallest at which the group
+masking and the wave tail can go wrong.  No test asserts flight quality: the reference's DSLPID loop diverges
+on this drone model.
+"""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+import ctrl_cases as cc  # noqa: E402
+from gym_pybullet_adrp_amd import _lib  # noqa: E402
+from gym_pybullet_adrp_amd.envs import CtrlAviary, HoverAviary, MultiHoverAviary, VelocityAviary  # noqa: E402
+from gym_pybullet_adrp_amd.utils import abi  # noqa: E402
+from gym_pybullet_adrp_amd.utils.enums import ActionType, Physics  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+from test_hover_gpu import FLOORS, GROUPS, PID_GROUPS, active_fields  # noqa: E402
+from test_multihover_gpu import (DOWNWASH, F32_ULP, NOISE, RTOL, UNCOUPLED, field_index, get_state, put_state,  # noqa: E402
+                                 real_of, stack_xyzs, stacked_state)
+
+SHAPES = [(40, 3), (9, 5)]
+ROW = (("pos", slice(0, 3)), ("quat", slice(3, 7)), ("rpy", slice(7, 10)), ("vel", slice(10, 13)), ("ang_v", slice(13, 16)))
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return cc.load()
+
+
+def gain32(a):
+    """float32 1 + 0.05 a, two roundings (BaseRLAviary.py:192)"""
+    a = np.asarray(a, np.float32)
+    return np.float32(1) + np.float32(0.05) * a
+
+
+def rpm_of(env, a):
+    """HOVER_RPM (1 + 0.05 a) as the env's precision computes it from a float32 a: what MultiHoverAviary and
+    HoverAviary apply for the action a"""
+    real = real_of(env)
+    return real(env.HOVER_RPM) * gain32(a).astype(real)
+
+
+def random_state(rng, env, tilt=0.25, vel=0.5, omega=2.0, pid=False):
+    """random airborne states, drone n of an env about (INIT_XYZS[n].xy, 1 + 0.4 n): [nf, E*N] float64
+    (representable in the env's precision) and ints replicated per env"""
+    E, N = env.num_envs, env.NUM_DRONES
+    idx, iidx, names = field_index(env)
+    K = E * N
+    f = np.zeros((len(names), K))
+    i = np.zeros((3, K), np.int32)
+    center = np.tile(np.column_stack([env.INIT_XYZS[:, :2], 1.0 + 0.4 * np.arange(N)]), (E, 1))
+    pos = center + rng.uniform(-0.3, 0.3, (K, 3))
+    rpy = rng.uniform(-tilt, tilt, (K, 3)) * np.array([1, 1, 4])
+    q = np.array([O.quat_from_euler(r) for r in rpy])
+    lag = np.array([O.quat_from_euler(r + rng.uniform(-0.01, 0.01, 3)) for r in rpy])
+    v = rng.uniform(-vel, vel, (K, 3))
+    w = rng.uniform(-omega, omega, (K, 3))
+    for k, ax in enumerate("xyz"):
+        f[idx[f"pos_{ax}"]] = pos[:, k]; f[idx[f"vel_{ax}"]] = v[:, k]
+        f[idx[f"omega_{ax}"]] = w[:, k]; f[idx[f"angv_{ax}"]] = w[:, k]
+    for k, ax in enumerate("xyzw"):
+        f[idx[f"quat_{ax}"]] = q[:, k]; f[idx[f"link_quat_{ax}"]] = lag[:, k]
+    for k in range(4):
+        f[idx[f"last_rpm_{k}"]] = rng.uniform(0.8, 1.2, K) * 16364.0
+    if pid:
+        for k, ax in enumerate("xyz"):
+            f[idx[f"pid_last_rpy_{ax}"]] = rpy[:, k] + rng.uniform(-0.02, 0.02, K)
+            f[idx[f"pid_int_pos_{ax}"]] = np.clip(rng.uniform(-2.5, 2.5, K), -2, 2) * (0.075 if ax == "z" else 1)
+            f[idx[f"pid_int_rpy_{ax}"]] = rng.uniform(-1, 1, K) * (1 if ax != "z" else 20)
+    S = env.PYB_STEPS_PER_CTRL
+    i[iidx["step_counter"]] = np.repeat(rng.integers(0, 200, E) * S, N)
+    i[iidx["episode"]] = np.repeat(rng.integers(1, 5, E), N)
+    return f.astype(real_of(env)).astype(np.float64), i
+
+
+def drone_oracle(env, n, act_type):
+    """the unchanged single-drone oracle standing in for drone n of every env: HoverAviary at the drone's
+    initial pose, no auto-reset"""
+    cfg = _lib.default_config(abi.TASK_HOVER)
+    for k in ("physics", "num_envs", "pyb_freq", "ctrl_freq", "precision", "link_frame_lag", "seed"):
+        setattr(cfg, k, getattr(env.cfg, k))
+    cfg.act_type = act_type
+    cfg.autoreset = 0
+    abi.set_vec(cfg.init_xyz[0], env.INIT_XYZS[n])
+    return O.Oracle(cfg)
+
+
+def to_oracle(orc, names_env, f, i, n, N):
+    """the env's columns of drone n into the oracle's snapshot (its ring fields stay zero)"""
+    onames, _ = orc.field_names()
+    fo = np.zeros((len(onames), f.shape[1] // N))
+    for k, nme in enumerate(names_env):
+        fo[onames.index(nme)] = f[k, n::N]
+    orc.set_state(fo, np.ascontiguousarray(i[:, n::N]))
+
+
+def from_oracle(orc, names_env, N, n, f_out, i_out):
+    onames, _ = orc.field_names()
+    fo, io = orc.get_state()
+    for k, nme in enumerate(names_env):
+        f_out[k, n::N] = fo[onames.index(nme)]
+    i_out[:, n::N] = io
+
+
+def assert_groups(fg, fo, idx, groups, rtol, what=""):
+    for g in sorted(groups):
+        rows = [idx[n] for n in GROUPS[g]]
+        err = cc.vec_err(fg[rows].T, fo[rows].T, FLOORS[g])
+        assert err.max() <= rtol, f"{what}{g}: max rel err {err.max():.3e} (column {err.argmax()})"
+
+
+def assert_rows(og, want, rtol, what=""):
+    """obs rows [K, 20] against float64 rows [K, >=20]: the five vectors and the RPM columns at the bar"""
+    og = og.astype(np.float64)
+    for nm, sl in ROW:
+        err = cc.vec_err(og[:, sl], want[:, sl], 1e-3)
+        assert err.max() <= rtol, f"{what}obs {nm}: max rel err {err.max():.3e} (row {err.argmax()})"
+    err = cc.vec_err(og[:, 16:20], want[:, 16:20], 1.0)
+    assert err.max() <= rtol, f"{what}obs rpm: max rel err {err.max():.3e} (row {err.argmax()})"
+
+
+def oracle_rows(fo, idx, physics):
+    """[K, 20] the reference row of a snapshot (rpy from the quaternion; ang_v is angv under DYN, else omega)"""
+    cols = lambda names: fo[[idx[n] for n in names]].T   # noqa: E731
+    quat = cols(GROUPS["quat"])
+    rpy = np.array([O.euler_from_quat(q) for q in quat])
+    return np.concatenate([cols(GROUPS["pos"]), quat, rpy, cols(GROUPS["vel"]),
+                           cols(GROUPS["angv" if physics == Physics.DYN else "omega"]), cols(GROUPS["last_rpm"])], 1)
+
+
+def assert_dummy_outputs(rew, te, tr, E):
+    assert rew.shape == (E,) and te.shape == (E,) and tr.shape == (E,) and te.dtype == torch.bool and tr.dtype == torch.bool
+    assert (rew == -1).all() and not te.any() and not tr.any()
+
+
+# ---------------------------------------------------------------------------------------------
+# 1  golden replay: the reference's own CtrlAviary / VelocityAviary (DYN) episodes, teacher-forced
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("case,N,S", cc.CTRL_CASES + cc.VEL_CASES)
+def test_golden_replay(fx, case, N, S, precision):
+    rtol = RTOL[precision]
+    vel = case.startswith("v")
+    acts = fx[f"{case}_act"]
+    E, T = acts.shape[:2]
+    cls = VelocityAviary if vel else CtrlAviary
+    env = cls(num_drones=N, physics=Physics.DYN, pyb_freq=240, ctrl_freq=240 // S, num_envs=E, precision=precision)
+    np.testing.assert_array_equal(env.INIT_XYZS, fx[f"{case}_init_xyzs"])
+    assert env.MAX_RPM == float(fx["MAX_RPM"]) and (not vel or env.SPEED_LIMIT == float(fx["SPEED_LIMIT"]))
+    idx, iidx, names = field_index(env)
+    assert ("pid_last_rpy_x" in names) == vel and not any(n.startswith("ring_") for n in names)
+    groups = {"pos", "quat", "vel", "omega", "angv", "last_rpm"} | (set(PID_GROUPS) if vel else set())
+    if not vel:
+        assert fx[f"{case}_clipped"].any()
+    for t in range(T):
+        before = cc.rows_before(fx, case, t).reshape(E * N, 23)
+        f = cc.fill_state(names, before, cc.ctl_before(fx, case, t).reshape(E * N, 9) if vel else None)
+        i = np.zeros((3, E * N), np.int32)
+        i[iidx["step_counter"]] = S * t
+        put_state(env, f, i)
+        if vel:
+            a = torch.from_numpy(acts[:, t])
+        else:   # the reference's float64 RPMs (make_ctrl_golden.py), unrounded into a float64 env
+            a = torch.from_numpy((env.HOVER_RPM * gain32(acts[:, t])).astype(real_of(env)))
+        obs, rew, te, tr, info = env.step(a)
+        torch.cuda.synchronize()
+        assert obs.shape == (E, N, 20) and obs.dtype == torch.float32 and info == {"answer": 42}
+        want = cc.rows_after(fx, case, t).reshape(E * N, 23)
+        what = f"{case} t={t} "
+        og = obs.cpu().numpy().reshape(E * N, 20)
+        assert_rows(og, want, rtol + F32_ULP, what)
+        if precision == "fp64" and not vel:   # the clipped float64 RPMs, rounded once
+            np.testing.assert_array_equal(og[:, 16:20], want[:, 16:20].astype(np.float32))
+        fg, ig = get_state(env)
+        ref = cc.fill_state(names, want, fx[f"{case}_ctl"][:, t].reshape(E * N, 9) if vel else None)
+        assert_groups(fg, ref, idx, groups, rtol, what)
+        assert_dummy_outputs(rew, te, tr, E)
+        np.testing.assert_array_equal(ig[iidx["step_counter"]], np.repeat(fx[f"{case}_counter"][:, t], N))
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 2  CtrlAviary, uncoupled modes: every drone against the unchanged single-drone oracle
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("E,N", SHAPES)
+@pytest.mark.parametrize("S", [5, 1])
+@pytest.mark.parametrize("physics", UNCOUPLED)
+def test_ctrl_against_single_drone_oracle(physics, S, E, N, precision):
+    rtol = RTOL[precision]
+    rng = np.random.default_rng(1000 * UNCOUPLED.index(physics) + 100 * S + N)
+    env = CtrlAviary(num_drones=N, physics=physics, pyb_freq=240, ctrl_freq=240 // S, num_envs=E, precision=precision)
+    assert env.kernel_name == f"ctrl_step<{'f64' if precision == 'fp64' else 'f32'},{physics.name},G{4 if N == 3 else 8}>"
+    orcs = [drone_oracle(env, n, abi.ACT_RPM) for n in range(N)]
+    idx, iidx, names = field_index(env)
+    f, i = random_state(rng, env)
+    groups = active_fields(physics) | {"last_rpm"}
+    real = real_of(env)
+    for t in range(3):
+        put_state(env, f, i)
+        for n, o in enumerate(orcs):
+            to_oracle(o, names, f, i, n, N)
+        a = rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)
+        rpm = np.array([O.hover_rpm(orcs[0].cfg, row) for row in a.reshape(-1, 4)]).reshape(E, N, 4)   # float64
+        for n, o in enumerate(orcs):
+            o.step(a[:, n:n + 1])
+        obs, rew, te, tr, _ = env.step(torch.from_numpy(rpm.astype(real)))
+        torch.cuda.synchronize()
+        fg, ig = get_state(env)
+        fo, io = np.zeros_like(fg), np.zeros_like(ig)
+        for n, o in enumerate(orcs):
+            from_oracle(o, names, N, n, fo, io)
+        assert_groups(fg, fo, idx, groups, rtol, f"t={t} ")
+        np.testing.assert_array_equal(ig[iidx["step_counter"]], io[iidx["step_counter"]])
+        np.testing.assert_array_equal(ig[iidx["episode"]], io[iidx["episode"]])
+        assert_rows(obs.cpu().numpy().reshape(E * N, 20), oracle_rows(fo, idx, physics), rtol + F32_ULP, f"t={t} ")
+        assert_dummy_outputs(rew, te, tr, E)
+        f, i = fo.astype(real).astype(np.float64), io      # teacher forcing: the oracles' state into both
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 3  CtrlAviary with one drone is HoverAviary(act=RPM), bit for bit
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("physics", UNCOUPLED)
+def test_one_drone_is_hover_aviary(physics, precision):
+    E = 67
+    rng = np.random.default_rng(300 + UNCOUPLED.index(physics))
+    kw = dict(physics=physics, num_envs=E, precision=precision)
+    ctrl = CtrlAviary(num_drones=1, initial_xyzs=[[0, 0, 0]], pyb_freq=240, ctrl_freq=30, **kw)
+    hover = HoverAviary(initial_xyzs=[0, 0, 0], autoreset=False, **kw)
+    idx, iidx, names = field_index(ctrl)
+    hidx, hiidx, hnames = field_index(hover)
+    drag = physics == Physics.PYB_DRAG
+    f, i = random_state(rng, ctrl, tilt=0.1, vel=0.2, omega=0.5)
+    fh = np.zeros((len(hnames), E))
+    for k, nme in enumerate(names):
+        fh[hidx[nme]] = f[k]
+    put_state(ctrl, f, i)
+    put_state(hover, fh, i)
+    rows = [hidx[n] for n in names]
+    same = torch.tensor([drag or not n.startswith("last_rpm") for n in names])   # (HoverAviary keeps last_rpm for the drag only)
+    for t in range(20):
+        a = rng.uniform(-1, 1, (E, 1, 4)).astype(np.float32)
+        rpm = torch.from_numpy(rpm_of(ctrl, a)).to(ctrl.device)
+        oc, _, _, _, _ = ctrl.step(rpm)
+        oh, _, _, _, _ = hover.step(torch.from_numpy(a).to(hover.device))
+        fc, ic = ctrl.get_state()
+        fh, ih = hover.get_state()
+        assert torch.equal(fc[same], fh[rows][same]), f"t={t}: state differs in {int((fc[same] != fh[rows][same]).sum())} values"
+        assert torch.equal(fc[[idx[f'last_rpm_{k}'] for k in range(4)]].T.reshape(E, 1, 4), rpm)
+        assert torch.equal(ic[iidx["step_counter"]], ih[hiidx["step_counter"]])
+        assert torch.equal(oc[..., 0:3], oh[..., 0:3]) and torch.equal(oc[..., 7:16], oh[..., 3:12]), f"t={t}"
+        assert torch.equal(oc[..., 16:20], rpm.float())
+    ctrl.close(); hover.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 4  downwash modes: MultiHoverAviary(act=RPM) from the same state with matching actions, bit for bit
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("E,N", [(40, 2), (40, 3), (9, 8)])
+@pytest.mark.parametrize("physics", DOWNWASH)
+def test_downwash_is_multihover_aviary(physics, E, N, precision):
+    rng = np.random.default_rng(400 + N + DOWNWASH.index(physics))
+    kw = dict(num_drones=N, physics=physics, pyb_freq=240, ctrl_freq=48, num_envs=E, precision=precision)
+    ctrl = CtrlAviary(**kw)
+    multi = MultiHoverAviary(autoreset=False, **kw)
+    assert ctrl.kernel_name == multi.kernel_name.replace("multihover_step", "ctrl_step").replace(",A4", "")
+    idx, iidx, names = field_index(ctrl)
+    midx, miidx, mnames = field_index(multi)
+    fm, im = stacked_state(rng, multi, equal_z=True)
+    put_state(multi, fm, im)
+    put_state(ctrl, fm[[midx[n] for n in names]], im)
+    rows = [midx[n] for n in names]
+    drag = physics == Physics.PYB_GND_DRAG_DW
+    same = torch.tensor([drag or not n.startswith("last_rpm") for n in names])
+    for t in range(4):
+        a = rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)
+        ctrl.step(torch.from_numpy(rpm_of(ctrl, a)))
+        multi.step(torch.from_numpy(a))
+        fc, ic = ctrl.get_state()
+        fg, ig = multi.get_state()
+        assert torch.equal(fc[same], fg[rows][same]), f"t={t}: state differs in {int((fc[same] != fg[rows][same]).sum())} values"
+        assert torch.equal(ic[iidx["step_counter"]], ig[miidx["step_counter"]])
+    ctrl.close(); multi.close()
+
+
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("cls", [CtrlAviary, VelocityAviary])
+def test_downwash_exchange_every_substep(cls, precision):
+    """one env.step of 8 sub-steps (240 / 30 Hz) against eight env.steps of one sub-step (240 / 240 Hz) with
+    the same RPMs: a kernel that read the neighbours once per launch misses by ~1e-3.  (VelocityAviary: a
+    CtrlAviary at 240 Hz fed the RPMs its controller chose: the controller runs once per env.step.)"""
+    E, N, rtol = 40, 3, RTOL[precision]
+    rng = np.random.default_rng(520)
+    kw = dict(num_drones=N, physics=Physics.PYB_DW, pyb_freq=240, num_envs=E, precision=precision)
+    coarse = cls(ctrl_freq=30, **kw)
+    fine = CtrlAviary(ctrl_freq=240, **kw)
+    idx, _, names = field_index(fine)
+    cidx, _, cnames = field_index(coarse)
+    fs, i = stacked_state(rng, fine, equal_z=False, vel=0.5, beta_margin=0.06)
+    fc = np.zeros((len(cnames), E * N))
+    for k, nme in enumerate(names):
+        fc[cidx[nme]] = fs[k]
+    put_state(fine, fs, i)
+    put_state(coarse, fc, i)
+    if cls is CtrlAviary:
+        act = torch.from_numpy(rpm_of(fine, rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)))
+    else:
+        act = rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)
+        act[..., 3] = np.abs(act[..., 3])
+        act = torch.from_numpy(act)
+    coarse.step(act)
+    rpm = act if cls is CtrlAviary else coarse.get_state()[0][[cidx[f"last_rpm_{k}"] for k in range(4)]].T.reshape(E, N, 4).contiguous()
+    for _ in range(8):
+        fine.step(rpm)
+    torch.cuda.synchronize()
+    gc, _ = get_state(coarse)
+    gf, _ = get_state(fine)
+    for g in sorted(active_fields(Physics.PYB_DW)):
+        a = gc[[cidx[n] for n in GROUPS[g]]]
+        b = gf[[idx[n] for n in GROUPS[g]]]
+        err = np.linalg.norm(a - b, axis=0) / np.maximum(np.linalg.norm(b, axis=0), FLOORS[g])
+        assert err.max() <= rtol, f"{g}: max rel err {err.max():.3e}"
+    coarse.close(); fine.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 5  VelocityAviary with one drone is HoverAviary(act=VEL), bit for bit, controller state included
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("physics", [Physics.PYB, Physics.DYN, Physics.PYB_GND, Physics.PYB_DRAG])
+def test_one_drone_velocity_is_hover_vel(physics, precision):
+    E = 67
+    rng = np.random.default_rng(350 + UNCOUPLED.index(physics))
+    kw = dict(physics=physics, pyb_freq=240, ctrl_freq=30, num_envs=E, precision=precision)
+    velo = VelocityAviary(num_drones=1, initial_xyzs=[[0, 0, 0]], **kw)
+    hover = HoverAviary(initial_xyzs=[0, 0, 0], act=ActionType.VEL, autoreset=False, **kw)
+    assert velo.SPEED_LIMIT == hover.SPEED_LIMIT
+    idx, iidx, names = field_index(velo)
+    hidx, hiidx, hnames = field_index(hover)
+    f, i = random_state(rng, velo, tilt=0.15, omega=1.0, pid=True)
+    fh = np.zeros((len(hnames), E))
+    for k, nme in enumerate(names):
+        fh[hidx[nme]] = f[k]
+    put_state(velo, f, i)
+    put_state(hover, fh, i)
+    rows = [hidx[n] for n in names]
+    drag = physics == Physics.PYB_DRAG
+    same = torch.tensor([drag or not n.startswith("last_rpm") for n in names])
+    for t in range(6):
+        a = rng.uniform(-1, 1, (E, 1, 4)).astype(np.float32)
+        a[::9, :, :3] = 0        # zero direction -> zero target velocity
+        a = torch.from_numpy(a).to(velo.device)
+        ov, _, _, _, _ = velo.step(a)
+        oh, _, _, _, _ = hover.step(a)
+        fv, iv = velo.get_state()
+        fh, ih = hover.get_state()
+        assert torch.equal(fv[same], fh[rows][same]), f"t={t}: state differs in {int((fv[same] != fh[rows][same]).sum())} values"
+        assert torch.equal(iv[iidx["step_counter"]], ih[hiidx["step_counter"]])
+        assert torch.equal(ov[..., 0:3], oh[..., 0:3]) and torch.equal(ov[..., 7:16], oh[..., 3:12]), f"t={t}"
+        assert torch.equal(ov[..., 16:20], fv[[idx[f"last_rpm_{k}"] for k in range(4)]].T.reshape(E, 1, 4).float())
+    velo.close(); hover.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 6  VelocityAviary, several drones: every drone against the oracle with act=VEL
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("E,N", SHAPES)
+@pytest.mark.parametrize("physics", [Physics.PYB, Physics.DYN, Physics.PYB_GND, Physics.PYB_DRAG])
+def test_velocity_against_single_drone_oracle(physics, E, N, precision):
+    rtol = RTOL[precision]
+    rng = np.random.default_rng(600 + 10 * UNCOUPLED.index(physics) + N)
+    env = VelocityAviary(num_drones=N, physics=physics, pyb_freq=240, ctrl_freq=48, num_envs=E, precision=precision)
+    assert env.kernel_name == f"velocity_step<{'f64' if precision == 'fp64' else 'f32'},{physics.name},G{4 if N == 3 else 8}>"
+    orcs = [drone_oracle(env, n, abi.ACT_VEL) for n in range(N)]
+    idx, iidx, names = field_index(env)
+    f, i = random_state(rng, env, tilt=0.15, omega=1.0, pid=True)
+    groups = active_fields(physics) | {"last_rpm"} | set(PID_GROUPS)
+    real = real_of(env)
+    for t in range(3):
+        put_state(env, f, i)
+        a = rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)
+        a[..., 3] = np.abs(a[..., 3])
+        a[::7, 0, :3] = 0
+        for n, o in enumerate(orcs):
+            to_oracle(o, names, f, i, n, N)
+            o.step(a[:, n:n + 1])
+        obs, rew, te, tr, _ = env.step(torch.from_numpy(a))
+        torch.cuda.synchronize()
+        fg, ig = get_state(env)
+        fo, io = np.zeros_like(fg), np.zeros_like(ig)
+        for n, o in enumerate(orcs):
+            from_oracle(o, names, N, n, fo, io)
+        assert_groups(fg, fo, idx, groups, rtol, f"t={t} ")
+        np.testing.assert_array_equal(ig[iidx["step_counter"]], io[iidx["step_counter"]])
+        og = obs.cpu().numpy().reshape(E * N, 20)
+        assert_rows(og, oracle_rows(fo, idx, physics), rtol + F32_ULP, f"t={t} ")   # (16:20 is the oracle's last_rpm)
+        assert_dummy_outputs(rew, te, tr, E)
+        f, i = fo.astype(real).astype(np.float64), io
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 7  reset: the initial poses, zero RPM columns; VelocityAviary keeps its controllers
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("cls", [CtrlAviary, VelocityAviary])
+def test_masked_reset(cls, precision):
+    E, N = 40, 3
+    rng = np.random.default_rng(700)
+    env = cls(num_drones=N, physics=Physics.PYB_DRAG, pyb_freq=240, ctrl_freq=48, num_envs=E, precision=precision)
+    vel = cls is VelocityAviary
+    idx, iidx, names = field_index(env)
+    obs0, info = env.reset()
+    assert info == {"answer": 42}
+    o0 = obs0.cpu().numpy()
+    np.testing.assert_allclose(o0[..., 0:3], np.broadcast_to(env.INIT_XYZS, (E, N, 3)), rtol=1e-6)
+    np.testing.assert_allclose(o0[..., 3:16], np.broadcast_to([0, 0, 0, 1] + [0] * 9, (E, N, 13)), atol=1e-7)
+    assert (o0[..., 16:20] == 0).all()
+    f, i = random_state(rng, env, pid=vel)
+    put_state(env, f, i)
+    a = rng.uniform(0.2, 1, (E, N, 4)).astype(np.float32)
+    obs, _, _, _, _ = env.step(torch.from_numpy(a if vel else rpm_of(env, a)))
+    stepped = obs.clone()
+    f1, i1 = get_state(env)
+    assert (stepped[..., 16:20] > 0).all()
+    mask = np.arange(E) % 2 == 0
+    obs, _ = env.reset(mask=mask)
+    torch.cuda.synchronize()
+    f2, i2 = get_state(env)
+    col = np.repeat(mask, N)
+    og = obs.cpu().numpy()
+    assert (og[mask][..., 16:20] == 0).all() and np.array_equal(og[~mask], stepped.cpu().numpy()[~mask])
+    np.testing.assert_array_equal(og[mask], o0[mask])
+    for k, nme in enumerate(names):
+        if nme.startswith("pid_"):
+            np.testing.assert_array_equal(f2[k], f1[k], err_msg=nme)      # kept, reset envs included
+        else:
+            np.testing.assert_array_equal(f2[k][~col], f1[k][~col], err_msg=nme)
+    assert (f2[[idx[f"last_rpm_{k}"] for k in range(4)]][:, col] == 0).all()
+    assert (i2[iidx["step_counter"]][col] == 0).all() and (i2[iidx["episode"]][col] == i1[iidx["episode"]][col] + 1).all()
+    np.testing.assert_array_equal(i2[:, ~col], i1[:, ~col])
+    if vel:
+        assert np.abs(f1[[idx[n] for n in cc.PID_NAMES]]).min(axis=1).max() > 0   # (the kept values are not zeros)
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 8  an env's results do not depend on the batch or the shard
+# ---------------------------------------------------------------------------------------------
+def run_steps(env, acts):
+    out = []
+    obs, _ = env.reset()
+    out.append((obs.clone(),) + tuple(x.clone() for x in env.get_state()))
+    for a in acts:
+        obs, rew, te, tr, _ = env.step(a)
+        out.append((obs.clone(),) + tuple(x.clone() for x in env.get_state()))
+    env.close()
+    return out
+
+
+@pytest.mark.parametrize("precision", ["fp64", "fp32"])
+@pytest.mark.parametrize("cls,physics", [(CtrlAviary, Physics.PYB_DW), (VelocityAviary, Physics.PYB_GND_DRAG_DW)])
+def test_shards_are_bit_identical(cls, physics, precision):
+    N, T, E = 3, 6, 40
+    rng = np.random.default_rng(71)
+    kw = dict(num_drones=N, initial_xyzs=stack_xyzs(N), physics=physics, pyb_freq=240, ctrl_freq=48, precision=precision,
+              seed=9, init_noise=NOISE)
+    if cls is CtrlAviary:
+        acts = [torch.from_numpy((16364.0 * rng.uniform(0.9, 1.1, (E, N, 4))).astype(np.float32)).cuda() for _ in range(T)]
+    else:
+        acts = [torch.from_numpy(rng.uniform(0, 1, (E, N, 4)).astype(np.float32)).cuda() for _ in range(T)]
+    whole = run_steps(cls(num_envs=E, **kw), acts)
+    one = run_steps(cls(num_envs=1, env_offset=17, **kw), [a[17:18].contiguous() for a in acts])
+    shard = run_steps(cls(num_envs=8, env_offset=32, **kw), [a[32:].contiguous() for a in acts])
+    assert not torch.equal(whole[0][0][0], whole[0][0][1])           # the reset noise differs per env
+    for t in range(T + 1):
+        obs, f, i = whole[t]
+        assert torch.equal(obs[17:18], one[t][0]) and torch.equal(obs[32:], shard[t][0]), f"t={t} obs"
+        assert torch.equal(f[:, 17 * N:18 * N], one[t][1]) and torch.equal(f[:, 32 * N:], shard[t][1]), f"t={t} state"
+        assert torch.equal(i[:, 17 * N:18 * N], one[t][2]) and torch.equal(i[:, 32 * N:], shard[t][2]), f"t={t} ints"
+
+
+# ---------------------------------------------------------------------------------------------
+# 9  the episode never ends
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cls", [CtrlAviary, VelocityAviary])
+def test_never_terminated_or_truncated(cls):
+    E, N = 9, 5
+    rng = np.random.default_rng(900)
+    env = cls(num_drones=N, num_envs=E, precision="fp32")
+    idx, iidx, names = field_index(env)
+    f, i = random_state(rng, env, pid=cls is VelocityAviary)
+    f[idx["pos_x"]] += 50.0; f[idx["pos_y"]] -= 30.0; f[idx["pos_z"]] += 20.0      # far outside every hover bound
+    i[iidx["step_counter"]] = 240 * 9                                                # past HoverAviary's 8 s
+    put_state(env, f, i)
+    for t in range(3):
+        a = np.full((E, N, 4), 0.5, np.float32) if cls is VelocityAviary else np.full((E, N, 4), 16000.0, np.float32)
+        obs, rew, te, tr, info = env.step(a)
+        assert_dummy_outputs(rew, te, tr, E)
+        assert info == {"answer": 42} and (obs[..., 0] > 40).all()
+        assert (env.get_state()[1][iidx["step_counter"]] == 240 * 9 + t + 1).all()
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# 10  a float64 env consumes float64 RPMs unrounded
+# ---------------------------------------------------------------------------------------------
+def test_float64_rpms_are_not_rounded():
+    E, N, S, physics = 40, 3, 5, Physics.PYB
+    rng = np.random.default_rng(1010)
+    env = CtrlAviary(num_drones=N, physics=physics, pyb_freq=240, ctrl_freq=240 // S, num_envs=E, precision="fp64")
+    orcs = [drone_oracle(env, n, abi.ACT_RPM) for n in range(N)]
+    idx, iidx, names = field_index(env)
+    f, i = random_state(rng, env)
+    a = rng.uniform(-1, 1, (E, N, 4)).astype(np.float32)
+    rpm = np.array([O.hover_rpm(orcs[0].cfg, row) for row in a.reshape(-1, 4)]).reshape(E, N, 4)
+    assert (rpm != rpm.astype(np.float32)).any()
+    fo, io = np.zeros_like(f), np.zeros_like(i)
+    for n, o in enumerate(orcs):
+        to_oracle(o, names, f, i, n, N)
+        o.step(a[:, n:n + 1])
+        from_oracle(o, names, N, n, fo, io)
+    rows = [idx[n] for n in GROUPS["vel"]]
+    errs = []
+    for act in (torch.from_numpy(rpm), torch.from_numpy(rpm.astype(np.float32))):
+        put_state(env, f, i)
+        env.step(act)
+        fg, _ = get_state(env)
+        errs.append(cc.vec_err(fg[rows].T, fo[rows].T, FLOORS["vel"]).max())
+        if act.dtype == torch.float64:
+            assert_groups(fg, fo, idx, active_fields(physics) | {"last_rpm"}, RTOL["fp64"])
+    print(f"velocity error after one step: float64 RPMs {errs[0]:.3e}, the same rounded to float32 {errs[1]:.3e}")
+    assert errs[0] <= RTOL["fp64"] < errs[1]
+    env.close()
+
+
+def test_helpers_and_bound_outputs():
+    E, N = 4, 3
+    env = CtrlAviary(num_drones=N, num_envs=E, neighbourhood_radius=0.3, precision="fp32")
+    env.reset()
+    adj = env.adjacency_matrix()
+    want = (np.linalg.norm(env.INIT_XYZS[:, None] - env.INIT_XYZS[None], axis=-1) < 0.3).astype(np.float32)
+    np.testing.assert_array_equal(adj.cpu().numpy(), np.broadcast_to(want, (E, N, N)))
+    np.testing.assert_allclose(env.min_pair_distance().cpu().numpy(), 4 * env.L * np.sqrt(2), rtol=1e-6)
+    assert env.step_bytes() > 0
+    outs = (torch.zeros((E, N, 20), device=env.device), torch.zeros(E, device=env.device),
+            torch.zeros(E, dtype=torch.bool, device=env.device), torch.ones(E, dtype=torch.bool, device=env.device))
+    env.bind_outputs(*outs)
+    obs, rew, te, tr, _ = env.step(np.full((E, N, 4), env.HOVER_RPM))
+    assert obs is outs[0] and (outs[1] == -1).all() and not outs[3].any() and (outs[0][..., 16:20] > 0).all()
+    with pytest.raises(ValueError):
+        env.bind_outputs(outs[0][:, :2], *outs[1:])
+    env.close()
