@@ -126,6 +126,24 @@ def load():
     lib.adrp_ppo_gradients.restype = I
     lib.adrp_ppo_destroy.argtypes = [P]
     lib.adrp_ppo_destroy.restype = None
+    lib.adrp_dslpid_default_params.argtypes = [I, P]
+    lib.adrp_dslpid_default_params.restype = I
+    lib.adrp_dslpid_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]
+    lib.adrp_dslpid_create.restype = I
+    lib.adrp_dslpid_destroy.argtypes = [P]
+    lib.adrp_dslpid_destroy.restype = None
+    lib.adrp_dslpid_reset.argtypes = [P, P, P]
+    lib.adrp_dslpid_reset.restype = I
+    lib.adrp_dslpid_set_gains.argtypes = [P, P]
+    lib.adrp_dslpid_set_gains.restype = I
+    lib.adrp_dslpid_get_state.argtypes = [P, P, P]
+    lib.adrp_dslpid_get_state.restype = I
+    lib.adrp_dslpid_set_state.argtypes = [P, P, P]
+    lib.adrp_dslpid_set_state.restype = I
+    lib.adrp_dslpid_compute.argtypes = [P, ctypes.c_double, P, P, P, I, I, P, P, P, P, P, P, P, P]
+    lib.adrp_dslpid_compute.restype = I
+    lib.adrp_dslpid_compute_env.argtypes = [P, ctypes.c_double, P, P, P, P, P, P, P, P, P]
+    lib.adrp_dslpid_compute_env.restype = I
     lib.adrp_compact_rows.argtypes = [P, P, P, I, I, I, P, P, P, P]
     lib.adrp_compact_rows.restype = I
     lib.adrp_memcpy_async.argtypes = [P, P, ctypes.c_size_t, I, P]

@@ -17,6 +17,8 @@ from datetime import datetime
 import numpy as np
 import torch
 
+from .utils import abi
+
 
 def logger_arrays(timestamps, states20, controls):
     """[T, n] times, [T, n, 20] state vectors, [T, n, 12] controls -> the arrays Logger.log
@@ -64,8 +66,9 @@ class DeviceLogger:
         self._rpm, self._ring = None, None
         if race:
             self._rpm = [idx[f"rpm_{k}"] for k in range(4)]
-        elif env.PHYSICS.name in ("PYB_DRAG", "PYB_GND_DRAG_DW"):
-            self._rpm = [idx[f"last_rpm_{k}"] for k in range(4)]      # maintained by the drag model
+        elif env.PHYSICS.name in ("PYB_DRAG", "PYB_GND_DRAG_DW") or env.cfg.task in (abi.TASK_CTRL, abi.TASK_VELOCITY):
+            # maintained by the drag model; CtrlAviary / VelocityAviary keep it in every physics mode
+            self._rpm = [idx[f"last_rpm_{k}"] for k in range(4)]
         elif env.ACT_TYPE.name in ("RPM", "ONE_D_RPM"):
             # last_clipped_action = HOVER_RPM * (1 + 0.05 a) of the newest ring entry
             A = env.h.A

@@ -31,6 +31,7 @@ RACE_COMPARE, RACE_COMPETE = 0, 1
 POLICY_TANH, POLICY_RELU = 0, 1
 POLICY_RAW, POLICY_RELATIVE, POLICY_ABSOLUTE = 0, 1, 2
 VEC_SLOTS = 4   # ADRP_VEC_SLOTS
+DSLPID_CF2X, DSLPID_CF2P = 0, 1
 
 _d = ctypes.c_double
 _i32 = ctypes.c_int32
@@ -145,3 +146,13 @@ class AdrpPpoCfg(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("normalize_advantage", _i32),
                 ("learning_rate", _d), ("clip_range", _d), ("clip_range_vf", _d),
                 ("ent_coef", _d), ("vf_coef", _d), ("max_grad_norm", _d)]
+
+
+class AdrpDslpidParams(ctypes.Structure):
+    """adrp_dslpid_params (include/adrp.h): gains, mixer and model constants of the stand-alone DSLPIDControl"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", _i32),
+                ("p_for", _arr(_d, 3)), ("i_for", _arr(_d, 3)), ("d_for", _arr(_d, 3)),
+                ("p_tor", _arr(_d, 3)), ("i_tor", _arr(_d, 3)), ("d_tor", _arr(_d, 3)),
+                ("mixer", _arr(_d, 4, 3)),
+                ("gravity", _d), ("kf", _d),
+                ("pwm2rpm_scale", _d), ("pwm2rpm_const", _d), ("min_pwm", _d), ("max_pwm", _d)]

@@ -476,6 +476,68 @@ int adrp_ppo_set_params(adrp_ppo_t* ppo, const float* params, const float* m, co
 int adrp_ppo_gradients(adrp_ppo_t* ppo, float* grad_out, void* stream);
 void adrp_ppo_destroy(adrp_ppo_t* ppo);
 
+/* ---------------------------------------------------------------------------------------
+ * Stand-alone batched DSLPIDControl (control/DSLPIDControl.py:9-259, control/BaseControl.py:21-95):
+ * what examples/pid.py:126-147 and examples/downwash.py build one object per drone of, for users who
+ * drive CtrlAviary themselves.  One controller handle holds `rows` independent controllers (one per
+ * (env, drone) pair, rows = E * N, row e * N + n), their state SoA [9][rows] on the device in the
+ * controller's precision: last_rpy 3, integral_pos_e 3, integral_rpy_e 3.  One kernel launch per
+ * compute call on the caller's stream, no allocation and no host synchronisation (capturable); the
+ * gains, the mixer and control_timestep travel by value with the launch, so a captured graph keeps the
+ * values it was captured with.  csrc/dslpid_kernel.h.
+ *
+ * Errors of these calls are reported through adrp_last_error(NULL).  Argument errors (rows <= 0,
+ * precision not 0 / 1, a struct_size mismatch, control_timestep <= 0, NULL pointers) are refused
+ * before any device call.
+ * --------------------------------------------------------------------------------------- */
+#define ADRP_DSLPID_CF2X 0          /* MIXER_MATRIX of DroneModel.CF2X (DSLPIDControl.py:47-53) */
+#define ADRP_DSLPID_CF2P 1          /* MIXER_MATRIX of DroneModel.CF2P (DSLPIDControl.py:54-60) */
+typedef struct adrp_dslpid adrp_dslpid_t;
+typedef struct adrp_dslpid_params {
+    uint32_t struct_size;           /* = sizeof(adrp_dslpid_params); checked by create / set_gains */
+    int32_t reserved;
+    double p_for[3], i_for[3], d_for[3];   /* P / I / D_COEFF_FOR (setPIDCoefficients) */
+    double p_tor[3], i_tor[3], d_tor[3];   /* P / I / D_COEFF_TOR */
+    double mixer[4][3];             /* MIXER_MATRIX */
+    double gravity;                 /* GRAVITY = g * m of the model's URDF (BaseControl.py:35) */
+    double kf;                      /* KF (BaseControl.py:37) */
+    double pwm2rpm_scale, pwm2rpm_const, min_pwm, max_pwm;   /* DSLPIDControl.py:43-46 */
+} adrp_dslpid_params;
+/* The reference's defaults (DSLPIDControl.py:37-60) for `model` (ADRP_DSLPID_CF2X / _CF2P), with
+ * gravity = 9.8 * m and kf of the model's URDF (cf2x_IROS.urdf m = 0.03454, cf2p.urdf m = 0.027). */
+int adrp_dslpid_default_params(int model, adrp_dslpid_params* p);
+int adrp_dslpid_create(int rows, int precision, const adrp_dslpid_params* p, int device, adrp_dslpid_t** out);
+void adrp_dslpid_destroy(adrp_dslpid_t* c);
+/* DSLPIDControl.reset (:65-78): zero the nine state values of all rows (mask_dev NULL) or of the rows
+ * with mask_dev[r] != 0 (uint8 [rows]).  control_counter is the caller's host-side count. */
+int adrp_dslpid_reset(adrp_dslpid_t* c, const uint8_t* mask_dev, void* stream);
+/* setPIDCoefficients: the six gain triples of *p replace the handle's (the other fields are ignored);
+ * later compute calls use them. */
+int adrp_dslpid_set_gains(adrp_dslpid_t* c, const adrp_dslpid_params* p);
+/* [9][rows] in the controller's precision (float32 / float64) */
+int adrp_dslpid_get_state(adrp_dslpid_t* c, void* st_dev, void* stream);
+int adrp_dslpid_set_state(adrp_dslpid_t* c, const void* st_dev, void* stream);
+/* computeControl of every row.  pos / quat (xyzw) / vel: component k of row r is base[r * row_stride + k];
+ * row_stride 0 means three packed arrays [rows][3] / [rows][4] / [rows][3], and rows of
+ * _getDroneStateVector's layout [rows][20] are passed as row, row + 3, row + 10 with row_stride 20.
+ * input_precision is the element type of the three (0 float32, 1 float64): the controller's own, or
+ * float32 into a float64 controller (converted on load); anything else is refused.  The targets are
+ * [rows][3] in the controller's precision, NULL = zeros (of target_rpy only the yaw enters,
+ * DSLPIDControl.py:200).  Outputs in the controller's precision: rpm_out [rows][4] (what adrp_step_rpm
+ * takes), pos_e_out [rows][3] or NULL, yaw_e_out [rows] or NULL: computed_target_rpy[2] - cur_rpy[2]
+ * (:145), the first the third angle of the intrinsic 'XYZ' decomposition of the target basis (:205). */
+int adrp_dslpid_compute(adrp_dslpid_t* c, double control_timestep, const void* pos_dev, const void* quat_dev,
+                        const void* vel_dev, int row_stride, int input_precision, const void* target_pos_dev,
+                        const void* target_rpy_dev, const void* target_vel_dev, const void* target_rpy_rates_dev,
+                        void* rpm_out, void* pos_e_out, void* yaw_e_out, void* stream);
+/* The same with pos / quat / vel read from the state columns of env handle h (pos_*, quat_*, vel_* of
+ * adrp_state_layout) in the handle's own precision: no float32 observation row in between, which is what
+ * lets a float64 loop follow the reference to 1e-9.  Refused: a MultiRaceAviary handle, a handle whose
+ * E * N or precision differs from the controller's, a handle in persistent mode. */
+int adrp_dslpid_compute_env(adrp_dslpid_t* c, double control_timestep, adrp_t* h, const void* target_pos_dev,
+                            const void* target_rpy_dev, const void* target_vel_dev, const void* target_rpy_rates_dev,
+                            void* rpm_out, void* pos_e_out, void* yaw_e_out, void* stream);
+
 /* SB3 VecEnv host path: the terminal observations of the finished envs, compacted on the device
  * behind the step's packed outputs so ONE device -> host copy returns them (replaces the per-env
  * infos[e]["terminal_observation"] = obs that stable_baselines3 DummyVecEnv.step_wait fills from
