@@ -126,6 +126,10 @@ def load():
     lib.adrp_ppo_gradients.restype = I
     lib.adrp_ppo_destroy.argtypes = [P]
     lib.adrp_ppo_destroy.restype = None
+    lib.adrp_episode_step.argtypes = [P, P, P, P, P]
+    lib.adrp_episode_step.restype = I
+    lib.adrp_episode_summary.argtypes = [P, P, P]
+    lib.adrp_episode_summary.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]
     lib.adrp_dslpid_default_params.restype = I
     lib.adrp_dslpid_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]

@@ -32,9 +32,13 @@ class RolloutCollector:
 
     policy: ``DevicePolicy`` with a critic (``set_critic`` / ``from_zip(critic=True)``), its input
     the first ``policy.in_dim`` obs floats of the agent's row; for MultiHoverAviary the whole joint
-    row (``in_dim == NUM_DRONES * D``, ``act_dim == NUM_DRONES * A``, raw mode)."""
+    row (``in_dim == NUM_DRONES * D``, ``act_dim == NUM_DRONES * A``, raw mode).
 
-    def __init__(self, env, policy, n_steps, gamma=0.99, gae_lambda=0.95, seed=0):
+    episode_stats: an ``evaluation.EpisodeStats`` of ``num_envs`` envs (SB3's Monitor window behind
+    rollout/ep_rew_mean / ep_len_mean): every step's env reward and flags are accounted there, before
+    the time-limit bootstrap is added to the stored reward.  None: ``collect`` launches what it always did."""
+
+    def __init__(self, env, policy, n_steps, gamma=0.99, gae_lambda=0.95, seed=0, episode_stats=None):
         if not policy.has_critic:
             raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
         N = env.NUM_DRONES
@@ -50,7 +54,9 @@ class RolloutCollector:
                 raise ValueError(f"a joint MultiHoverAviary policy emits NUM_DRONES * A = {N * env.h.A} raw actions")
         elif policy.in_dim > D:
             raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
-        self.env, self.policy = env, policy
+        if episode_stats is not None and (episode_stats.E != env.num_envs or episode_stats.device != env.device):
+            raise ValueError("episode_stats must hold num_envs envs on the env's device")
+        self.env, self.policy, self.episode_stats = env, policy, episode_stats
         self.T, self.E = int(n_steps), env.num_envs
         self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
         dev = env.device
@@ -95,7 +101,7 @@ class RolloutCollector:
             return self._collect()
 
     def _collect(self):
-        env, pol, E = self.env, self.policy, self.E
+        env, pol, E, meter = self.env, self.policy, self.E, self.episode_stats
         base = self.rollouts * self.T
         env_act = self._env_act.view(E, -1)
         for t in range(self.T):
@@ -107,6 +113,8 @@ class RolloutCollector:
             self.rewards[t].copy_(rew)
             self._term[t].copy_(term)
             self._trunc[t].copy_(trunc)
+            if meter is not None:
+                meter.step(rew, term, trunc)      # the env's own reward (Monitor sits below the bootstrap)
             # time-limit bootstrap (collect_rollouts): reward += gamma * V(terminal obs) only where the
             # episode was truncated and not terminated; a select, so a stale terminal row of an env
             # that did not finish (even a non-finite one) never reaches its reward

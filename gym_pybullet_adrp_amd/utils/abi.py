@@ -156,3 +156,11 @@ class AdrpDslpidParams(ctypes.Structure):
                 ("mixer", _arr(_d, 4, 3)),
                 ("gravity", _d), ("kf", _d),
                 ("pwm2rpm_scale", _d), ("pwm2rpm_const", _d), ("min_pwm", _d), ("max_pwm", _d)]
+
+
+class AdrpEpisodeIO(ctypes.Structure):
+    """adrp_episode_io (include/adrp.h): the caller-owned device buffers of the on-device episode statistics"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("capacity", _i32), ("ring", _i32),
+                ("quota", _p), ("run_return", _p), ("run_length", _p), ("count", _p), ("meta", _p),
+                ("log_return", _p), ("log_length", _p), ("log_env", _p)]

@@ -477,6 +477,53 @@ int adrp_ppo_gradients(adrp_ppo_t* ppo, float* grad_out, void* stream);
 void adrp_ppo_destroy(adrp_ppo_t* ppo);
 
 /* ---------------------------------------------------------------------------------------
+ * On-device episode statistics (examples/learn.py:82-94, 142; scripts/sim.py:62-108): the episode
+ * accounts stable_baselines3 2.3.2 keeps on the host, restated from its published code (not pinned
+ * against an SB3 run): evaluation.py evaluate_policy's per-step `for i in range(n_envs)` loop
+ * (current_rewards / current_lengths, episode_counts < episode_count_targets, the episode_rewards /
+ * episode_lengths lists) and the Monitor window behind rollout/ep_rew_mean / ep_len_mean
+ * (on_policy_algorithm.py ep_info_buffer = deque(maxlen=stats_window_size), utils.safe_mean).
+ * Handle-less: the caller owns every buffer (all on one device) and passes them in one struct; every
+ * pointer is fixed per step, so a step can be captured in a HIP graph.  csrc/episode.hip.
+ *
+ * adrp_episode_step: one launch (one workgroup) per env.step on the step's rew [E] float32 and
+ * term / trunc [E] uint8.  Per env: run_return += (double)rew, run_length += 1.  Env e finishes when
+ * term | trunc and is logged when quota is NULL or count[e] < quota[e].  The logged finishers of a step
+ * are ranked by ascending env index (the order SB3's loop appends in); rank r goes to position
+ * total + r (total = meta[0] before the step).  ring == 0: slot = position while it is < capacity,
+ * otherwise the episode is only counted (meta[3]).  ring == 1: slot = position mod capacity, and of a
+ * step with k > capacity logged finishers only ranks >= k - capacity are written (one writer per slot):
+ * the log holds what deque(maxlen=capacity) holds.  A logged env gets count[e] += 1 and its run_return /
+ * run_length go back to 0; those of an env past its quota are unspecified.  meta[0] += k, meta[2] += 1,
+ * meta[1] is recomputed.  No atomics: equal inputs give equal bits.
+ *
+ * adrp_episode_summary: out8 (device, 8 doubles) = {n, mean return, std return (ddof 0, np.std), min
+ * return, max return, mean length, std length, total} over the n = min(total, capacity) logged
+ * episodes; double arithmetic in a fixed order, two-pass variance; n = 0 gives NaN (safe_mean).
+ *
+ * Errors are reported through adrp_last_error(NULL).  Refused with ADRP_ERR_INVALID before any device
+ * call: NULL io, a struct_size mismatch, num_envs < 1, capacity < 1, ring not 0 / 1, a NULL buffer other
+ * than quota, NULL rew / term / trunc / out8.
+ * --------------------------------------------------------------------------------------- */
+typedef struct adrp_episode_io {
+    uint32_t struct_size;     /* sizeof(adrp_episode_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  capacity;        /* C >= 1 log slots */
+    int32_t  ring;            /* 0: log the first C episodes (evaluation); 1: keep the last C (Monitor window) */
+    const int32_t* quota;     /* int32 [E] or NULL: env e is logged only while count[e] < quota[e] */
+    double*  run_return;      /* [E] running sum of the current episode (float64, as SB3's current_rewards) */
+    int32_t* run_length;      /* [E] */
+    int32_t* count;           /* [E] episodes logged for env e */
+    int64_t* meta;            /* [4]: total episodes logged, remaining = sum_e max(0, quota[e] - count[e])
+                                 (0 without quota), steps taken, episodes dropped (ring == 0 and the log is full) */
+    double*  log_return;      /* [C] */
+    int32_t* log_length;      /* [C] */
+    int32_t* log_env;         /* [C] */
+} adrp_episode_io;
+int adrp_episode_step(const adrp_episode_io* io, const float* rew, const uint8_t* term, const uint8_t* trunc, void* stream);
+int adrp_episode_summary(const adrp_episode_io* io, double* out8, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Stand-alone batched DSLPIDControl (control/DSLPIDControl.py:9-259, control/BaseControl.py:21-95):
  * what examples/pid.py:126-147 and examples/downwash.py build one object per drone of, for users who
  * drive CtrlAviary themselves.  One controller handle holds `rows` independent controllers (one per
