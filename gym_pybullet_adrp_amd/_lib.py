@@ -130,6 +130,14 @@ def load():
     lib.adrp_episode_step.restype = I
     lib.adrp_episode_summary.argtypes = [P, P, P]
     lib.adrp_episode_summary.restype = I
+    lib.adrp_race_controllers.argtypes = [P, ctypes.c_double, P]
+    lib.adrp_race_controllers.restype = I
+    lib.adrp_race_results_begin.argtypes = [P, I, I, P]
+    lib.adrp_race_results_begin.restype = I
+    lib.adrp_race_results_step.argtypes = [P, P, P, P, P, P, P]
+    lib.adrp_race_results_step.restype = I
+    lib.adrp_race_results_step_env.argtypes = [P, P, P, P, P, P]
+    lib.adrp_race_results_step_env.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]
     lib.adrp_dslpid_default_params.restype = I
     lib.adrp_dslpid_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]

@@ -32,6 +32,7 @@ POLICY_TANH, POLICY_RELU = 0, 1
 POLICY_RAW, POLICY_RELATIVE, POLICY_ABSOLUTE = 0, 1, 2
 VEC_SLOTS = 4   # ADRP_VEC_SLOTS
 DSLPID_CF2X, DSLPID_CF2P = 0, 1
+RACE_CTRL_NONE, RACE_CTRL_HARDCODED, RACE_CTRL_POLICY = 0, 1, 2
 
 _d = ctypes.c_double
 _i32 = ctypes.c_int32
@@ -164,3 +165,21 @@ class AdrpEpisodeIO(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("capacity", _i32), ("ring", _i32),
                 ("quota", _p), ("run_return", _p), ("run_length", _p), ("count", _p), ("meta", _p),
                 ("log_return", _p), ("log_length", _p), ("log_env", _p)]
+
+
+class AdrpRaceCtrlIO(ctypes.Structure):
+    """adrp_race_ctrl_io (include/adrp.h): the caller-owned device buffers of the race evaluation's controller launch"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("ref_len", _i32),
+                ("kind", _arr(_i32, MAX_DRONES)),
+                ("ref", _p), ("offset", _p), ("phase", _p), ("setpoints", _p), ("codes", _p), ("args", _p)]
+
+
+class AdrpRaceResultsIO(ctypes.Structure):
+    """adrp_race_results_io (include/adrp.h): the caller-owned device buffers of the per-drone race results"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("capacity", _i32),
+                ("base", _i32), ("reserved", _i32),
+                ("open", _p), ("run_return", _p), ("run_length", _p), ("gates", _p), ("finish", _p), ("elim", _p),
+                ("meta", _p), ("log_return", _p), ("log_length", _p), ("log_term", _p), ("log_trunc", _p),
+                ("log_gates", _p), ("log_finish", _p), ("log_elim", _p)]

@@ -524,6 +524,90 @@ int adrp_episode_step(const adrp_episode_io* io, const float* rew, const uint8_t
 int adrp_episode_summary(const adrp_episode_io* io, double* out8, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched race evaluation (scripts/sim.py:18-112 simulate(): one controller per drone, n_runs episodes, the
+ * episode times): the two per-step pieces of that loop that are not the env step.  csrc/sim_kernel.h,
+ * gym_pybullet_adrp_amd/sim.py.  Handle-less like the episode statistics: the caller owns every buffer (all
+ * on one device), every pointer is fixed per step, so a wave's step sequence can be captured in a HIP graph.
+ *
+ * adrp_race_controllers: one launch per step, one lane per (env, drone), slot e * N + n.  Writes the command
+ * arrays adrp_race_command takes, codes int32 [E,N] and args float64 [E,N,ADRP_CMD_ARGS], every slot on every
+ * step (zeros included).  kind[n] picks drone n's controller:
+ *   NONE       code ADRP_CMD_NONE, zeros.
+ *   HARDCODED  user_controller/HardCodedController.py:117-190 as hardcoded.HardCodedCommander.predict restates
+ *              it, bit for bit: step = clamp(trunc(ep_time * 25) - offset, 0, ref_len); TAKEOFF [0.3, 2] before
+ *              take-off; FULLSTATE (ref[step], 0, 0.5, 0, 0, ep_time) while step < ref_len; then one NOTIFY
+ *              [ep_time], one LAND [0, 2], then NONE.  ref float64 [E,N,ref_len,3] (the spline samples), offset
+ *              int64 [E,N] ((2 + delay) * 25), phase uint8 [3][E*N] (took off, notified, landed), which the
+ *              kernel updates.
+ *   POLICY     RLController._action_transform (RLController.py:62-73): FULLSTATE with args[0:3] = the setpoint's
+ *              x, y, z, args[9] = its yaw, args[13] = ep_time, the rest 0.  setpoints float32 [N][E][4],
+ *              drone-major: what adrp_policy_act of drone n's policy writes from the rows obs_dev + n * D with
+ *              rows = E and obs_stride = N * D, before this launch on the same stream.
+ *
+ * adrp_race_results_*: the per-drone twin of adrp_episode_step for envs without auto-reset, run in waves of
+ * E episodes.  adrp_race_results_begin(io, base, n_open) opens a wave: running arrays to zero, finish / elim
+ * to -1, open[e] = e < n_open, meta[1] = n_open, and io->base = base (a host field that travels with every
+ * later step launch).  adrp_race_results_step: one launch (one workgroup) per env.step, after it, on the
+ * step's rew [E] float32, term / trunc [E] uint8 and the per-drone gate / flags int32 [E*N] of the race state
+ * (adrp_state_field "gate" / "flags": bit 0 eliminated, bit 1 finished).  For each env with open[e] != 0:
+ * run_return += (double)rew, run_length += 1; per drone gates = gate, finish = run_length the first time
+ * flags & 2, elim = run_length the first time flags & 1 (a drone may have both).  On term | trunc the episode
+ * goes to log slot base + e (one writer per slot) and open[e] = 0: later steps change nothing of it.
+ * meta[0] += episodes closed, meta[1] = envs still open (a fixed-order count, no atomic), meta[2] += 1.
+ * adrp_race_results_step_env reads gate / flags from handle h's own device image in place.
+ *
+ * Errors are reported through adrp_last_error(NULL).  Refused with ADRP_ERR_INVALID before any device call:
+ * a NULL io, a struct_size mismatch, num_envs < 1, num_drones outside 1..ADRP_MAX_DRONES, capacity < 1,
+ * base < 0 or base + n_open > capacity, n_open outside 0..num_envs, a kind outside the three, a NULL required
+ * buffer, HARDCODED without ref / offset / phase (or ref_len < 1), POLICY without setpoints, NULL gate / flags /
+ * rew / term / trunc, a NULL or non-race handle, a handle whose E, N differ from the io's.
+ * --------------------------------------------------------------------------------------- */
+#define ADRP_RACE_CTRL_NONE 0
+#define ADRP_RACE_CTRL_HARDCODED 1
+#define ADRP_RACE_CTRL_POLICY 2
+typedef struct adrp_race_ctrl_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_ctrl_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  ref_len;         /* L: samples per reference trajectory (HARDCODED) */
+    int32_t  kind[ADRP_MAX_DRONES];   /* ADRP_RACE_CTRL_* of drone n < N */
+    const double*  ref;       /* [E][N][L][3] or NULL without a HARDCODED drone */
+    const int64_t* offset;    /* [E][N], likewise */
+    uint8_t* phase;           /* [3][E*N], likewise */
+    const float* setpoints;   /* [N][E][4] or NULL without a POLICY drone */
+    int32_t* codes;           /* [E][N] out */
+    double*  args;            /* [E][N][ADRP_CMD_ARGS] out, 16-byte aligned */
+} adrp_race_ctrl_io;
+typedef struct adrp_race_results_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_results_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  capacity;        /* C >= 1 log slots */
+    int32_t  base;            /* log slot of env 0 in the current wave (set by adrp_race_results_begin) */
+    int32_t  reserved;
+    uint8_t* open;            /* [E] the env's episode is still running */
+    double*  run_return;      /* [E] */
+    int32_t* run_length;      /* [E] */
+    int32_t* gates;           /* [E][N] gates passed so far */
+    int32_t* finish;          /* [E][N] step the drone finished at, -1 = not yet */
+    int32_t* elim;            /* [E][N] step the drone was eliminated at, -1 = not yet */
+    int64_t* meta;            /* [4]: episodes logged, envs still open, steps taken, unused */
+    double*  log_return;      /* [C] */
+    int32_t* log_length;      /* [C] */
+    uint8_t* log_term;        /* [C] */
+    uint8_t* log_trunc;       /* [C] */
+    int32_t* log_gates;       /* [C][N] */
+    int32_t* log_finish;      /* [C][N] */
+    int32_t* log_elim;        /* [C][N] */
+} adrp_race_results_io;
+int adrp_race_controllers(const adrp_race_ctrl_io* io, double ep_time, void* stream);
+int adrp_race_results_begin(adrp_race_results_io* io, int base, int n_open, void* stream);
+int adrp_race_results_step(const adrp_race_results_io* io, const int32_t* gate, const int32_t* flags, const float* rew,
+                           const uint8_t* term, const uint8_t* trunc, void* stream);
+int adrp_race_results_step_env(const adrp_race_results_io* io, adrp_t* h, const float* rew, const uint8_t* term,
+                               const uint8_t* trunc, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Stand-alone batched DSLPIDControl (control/DSLPIDControl.py:9-259, control/BaseControl.py:21-95):
  * what examples/pid.py:126-147 and examples/downwash.py build one object per drone of, for users who
  * drive CtrlAviary themselves.  One controller handle holds `rows` independent controllers (one per
