@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/adrp.h"
@@ -83,6 +84,41 @@ struct adrp_handle {
     } while (0)
 
 constexpr int kBlock = kStepBlock;
+
+// launch a kernel; while adrp_profile_begin has a slot free, with start / stop events recorded by the
+// dispatch itself into the next one
+template <typename K, typename... Args>
+inline void launch_profiled(adrp_t* h, K kernel, dim3 grid, dim3 blk, hipStream_t s, const Args&... args) {
+    if (h->prof_n < h->prof_cap) {
+        hipExtLaunchKernelGGL(kernel, grid, blk, 0, s, h->ev_start[h->prof_n], h->ev_stop[h->prof_n], 0, args...);
+        ++h->prof_n;
+    } else {
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, args...);
+    }
+}
+
+// f(std::integral_constant) of a runtime physics code / of the lane-group width of N drones: the value
+// as a template argument (generic lambdas: constexpr int PH = decltype(ph)::value)
+template <typename F>
+inline void with_physics(int code, F&& f) {
+    switch (code) {
+        case ADRP_PHYS_PYB: f(std::integral_constant<int, ADRP_PHYS_PYB>{}); break;
+        case ADRP_PHYS_DYN: f(std::integral_constant<int, ADRP_PHYS_DYN>{}); break;
+        case ADRP_PHYS_PYB_GND: f(std::integral_constant<int, ADRP_PHYS_PYB_GND>{}); break;
+        case ADRP_PHYS_PYB_DRAG: f(std::integral_constant<int, ADRP_PHYS_PYB_DRAG>{}); break;
+        case ADRP_PHYS_PYB_DW: f(std::integral_constant<int, ADRP_PHYS_PYB_DW>{}); break;
+        default: f(std::integral_constant<int, ADRP_PHYS_PYB_GND_DRAG_DW>{}); break;
+    }
+}
+template <typename F>
+inline void with_group(int N, F&& f) {
+    switch (mh_group(N)) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
 
 inline int race_group(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8; }
 

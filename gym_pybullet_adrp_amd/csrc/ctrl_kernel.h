@@ -8,12 +8,11 @@
 //   VelocityAviary._preprocessAction (DSLPIDControl)         envs/VelocityAviary.py:129-168
 //   reward -1, terminated / truncated False                  envs/CtrlAviary.py:144-185
 //
-// Lane mapping, inactive lanes and the downwash exchange are multihover_kernel.h's: groups of G aligned
-// lanes (G = the next power of two >= N), a workgroup is one wave, lanes n >= N and groups past E run
-// the same instruction stream on a benign state (at rest one metre up, zero action: zero RPMs, or for
+// Lane mapping and inactive lanes are multihover_step_kernel's (lane_group.h): groups of G aligned lanes
+// (G = the next power of two >= N), a workgroup is one wave, lanes n >= N and groups past E run the same
+// instruction stream on a benign state (at rest one metre up, zero action: zero RPMs, or for
 // VelocityAviary the zero-direction target velocity), load nothing and store nothing.  The downwash
-// body below is a second copy of multihover_step_kernel's lambda, kept apart so that MultiHoverAviary's
-// translation units compile exactly as before; tests/test_ctrl_gpu.py pins the two to the same bits.
+// exchange is the one Downwash functor of lane_group.h that multihover_step_kernel calls too.
 //
 // State: HoverAviary's base float fields with E N columns, column e N + n, no action ring (these envs
 // have no action history); last_rpm_* is written in every physics mode (it is the obs row's last four
@@ -56,8 +55,8 @@ __device__ __forceinline__ void ctrl_write_row(float* __restrict__ row, const fl
 template <typename Real, int PH, int G, int CTL>
 __global__ void __launch_bounds__(kStepBlock) ctrl_step_kernel(HoverArgs<Real> a, const CtrlConst<Real>* kp,
                                                                const Real* __restrict__ rpm_real) {
-    static_assert(G == 1 || G == 2 || G == 4 || G == 8, "lane-group width");
     static_assert(CTL == 0 || CTL == ADRP_ACT_VEL, "raw RPMs or the fused velocity controller");
+    static_assert(G == 1 || G == 2 || G == 4 || G == 8, "lane-group width");
     static_assert(kStepBlock == 64, "a workgroup is one wave: no group straddles it");
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DYN = (PH == ADRP_PHYS_DYN);
@@ -65,15 +64,16 @@ __global__ void __launch_bounds__(kStepBlock) ctrl_step_kernel(HoverArgs<Real> a
     constexpr bool DW = (PH == ADRP_PHYS_PYB_DW || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     const HoverConst<Real>& C = *a.c;
     const MultiConst<Real>& M = kp->m;
-    const int N = M.N, E = a.E;
+    const int N = M.N;
+    // (spelled out in both grouped step kernels: behind a shared lane descriptor they measured 0.04-0.12 us slower)
+    const int E = a.E;
     const long long t = (long long)blockIdx.x * kStepBlock + threadIdx.x;
     const long long eg = t / G;
     const int n = int(t % G);
     const bool live = eg < E && n < N;
     const int e = live ? int(eg) : 0;
     const size_t EN = size_t(E) * N, col = size_t(e) * N + n;   // (col is only used by live lanes)
-    HoverArgs<Real> ac = a;   // the column view of the state for load_body / store_body
-    ac.E = int(EN);
+    const HoverArgs<Real> ac = mh_columns(a, EN);
     // ---- loads (live lanes); inactive lanes rest one metre up with a zero action ----
     float act[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     Real rpm[4] = {Real(0), Real(0), Real(0), Real(0)};
@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(kStepBlock) ctrl_step_kernel(HoverArgs<Real> a
     for (int k = 0; k < HF_NPID; ++k) ctl[k] = Real(0);
     int32_t sc = 0;
     const bool lag = C.link_lag && !DYN;
-    Body<Real> b;
+    Body<Real> b;   // (spelled out too: behind a function call the float64 PYB_DRAG G = 8 kernel takes two more AGPRs)
     b.pos = v3(Real(0), Real(0), Real(1));
     b.q = {Real(0), Real(0), Real(0), Real(1)};
     b.ql = b.q;
@@ -121,26 +121,7 @@ __global__ void __launch_bounds__(kStepBlock) ctrl_step_kernel(HoverArgs<Real> a
     if constexpr (DYN) {
         for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
     } else if constexpr (DW) {
-        // _downwash (BaseAviary.py:792-818) as in multihover_step_kernel: every sub-step from the group's
-        // current positions, partners in the order n + 1, n + 2, ... (mod G), G - 1 terms, along the z
-        // axis of the cached link basis through the centre of mass
-        const Real dw1 = M.dw1, dw2 = M.dw2, dw3 = M.dw3, prop_r = M.prop_r;
-        auto downwash = [&](const Body<Real>& bb, const Chain<Real>& st) {
-            Real tsum = Real(0);
-#pragma unroll
-            for (int r = 1; r < G; ++r) {
-                const int k = (n + r) & (G - 1);
-                const Real ox = grp_rot<G>(bb.pos.x, r, n), oy = grp_rot<G>(bb.pos.y, r, n), oz = grp_rot<G>(bb.pos.z, r, n);
-                const Real dz = oz - bb.pos.z, dx = ox - bb.pos.x, dy = oy - bb.pos.y;
-                const Real dxy2 = dx * dx + dy * dy;
-                const Real kk = prop_r * rcp_nc_(Real(4) * dz);
-                const Real rb = rcp_nc_(dw2 * dz + dw3);
-                const Real term = dw1 * kk * kk * dw_exp(Real(-0.5) * (dxy2 * rb * rb), f64::kExp2Tab32);
-                tsum += (k < N && dz > Real(0) && dxy2 < Real(100)) ? term : Real(0);
-            }
-            const V3<Real> z = GND ? st.zc : st.zs;
-            return v3(-tsum * z.x, -tsum * z.y, -tsum * z.z);
-        };
+        const Downwash<Real, G, GND> downwash = {M.dw1, M.dw2, M.dw3, M.prop_r, n, N};
         touched = pyb_chain<Real, PH, 0, DRAG>(C, b, rpm, lag, downwash);
     } else {
         touched = pyb_chain<Real, PH, 0, DRAG>(C, b, rpm, lag, NoExtForce{});
@@ -171,24 +152,10 @@ __global__ void __launch_bounds__(kStepBlock) ctrl_step_kernel(HoverArgs<Real> a
 // fields are left as they are
 template <typename Real>
 __global__ void __launch_bounds__(256) ctrl_reset_kernel(HoverArgs<Real> a, const CtrlConst<Real>* kp) {
-    const MultiConst<Real>& M = kp->m;
-    const size_t EN = size_t(a.E) * M.N;
-    const size_t col = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (col >= EN) return;
-    const int e = int(col / M.N), n = int(col % M.N);
-    if (a.mask && !a.mask[e]) return;
-    const HoverConst<Real>& C = *a.c;
-    const bool dyn = C.physics == ADRP_PHYS_DYN;
-    HoverArgs<Real> ac = a;
-    ac.E = int(EN);
+    size_t EN, col;
     Body<Real> b;
-    int32_t sc = 0, ep = a.ist[HI_EPISODE * EN + col];
-    mh_reset_state(a, C, M, e, n, b, sc, ep);
-    store_body(ac, int(col), b, C.link_lag && !dyn, true, dyn);
-    a.ist[HI_STEP * EN + col] = sc;
-    a.ist[HI_EPISODE * EN + col] = ep;
     float o12[12];
-    hover_obs12(C, b, o12);
+    if (!mh_reset_column(a, kp->m, true, EN, col, b, o12)) return;
     ctrl_write_row(a.obs + col * size_t(kCtrlObs), o12, b.q, b.prev_rpm);
 }
 

@@ -7,15 +7,11 @@
 //   _dslPIDAttitudeControl              control/DSLPIDControl.py:212-259
 //   BaseControl.computeControlFromState control/BaseControl.py:55-95 (state[0:3], [3:7], [10:13])
 //
-// This is the second copy of the controller core: the first, dslpid_rpm (hover_kernel.h), is fused into
-// the HoverAviary / VelocityAviary step kernels with the targets of their action types, the default
-// gains and the CF2X mixer compiled in, and stays as it is.  Here the four targets, the gains, the mixer
-// and control_timestep are runtime values, and pos_e and the yaw error are returned.  The conventions are
-// the fused copy's: the scipy Euler round trip of the target rotation (:205, :242-244) is the identity
-// on a proper rotation, so the target basis is used directly; the clips are compare-selects; the current
-// Euler angles come from the accurate conversion (the attitude D term scales their error by
-// D_COEFF_TOR / control_timestep, about 1e6 at 48 Hz).  tests/test_dslpid_gpu.py holds the two copies
-// together.
+// The position and attitude loops are dslpid_core.h's, the one copy that dslpid_rpm (hover_kernel.h), the
+// controller fused into the HoverAviary / VelocityAviary step kernels, calls too.  That one has the
+// targets of its action types, the default gains and the CF2X mixer compiled in; here the four targets,
+// the gains, the mixer and control_timestep are runtime values, and pos_e and the yaw error are returned.
+// tests/test_dslpid_gpu.py compares the two callers.
 //
 // The yaw error is computed_target_rpy[2] - cur_rpy[2] (:145): the first is the THIRD angle of scipy's
 // intrinsic 'XYZ' decomposition of the target basis T = [x y z] = Rx(a) Ry(b) Rz(c) (:205), i.e.
@@ -32,6 +28,7 @@
 #pragma once
 
 #include "adrp_device.h"
+#include "dslpid_core.h"
 
 namespace adrp {
 
@@ -71,11 +68,6 @@ struct DslpidArgs {
     int rows;
 };
 
-template <typename Real>
-__device__ __forceinline__ Real clip_(Real x, Real lo, Real hi) {
-    return x < lo ? lo : (x > hi ? hi : x);
-}
-
 // computed_target_rpy[2] - cur_rpy[2] (:145): c = atan2(-y_ax.x, x_ax.x) minus getEulerFromQuaternion's yaw.
 // It is a difference of two angles of order one that goes to zero as the drone reaches its yaw target, so in
 // float32 the two roundings of the angles (1.2e-7 apart near 1 rad) would be all that is left of it.  The
@@ -108,44 +100,11 @@ __device__ __forceinline__ void dslpid_control(const DslpidConst<Real>& K, V3<Re
                                                Real ctl[kDslpidState], Real rpm[4], Real pos_e[3], bool want_yaw_e, Real& yaw_e) {
     const M3<Real> R = rot(q);
     const V3<Real> rpy = euler_xyz(q);
-    // _dslPIDPositionControl (:149-208)
-    const Real cp[3] = {pos.x, pos.y, pos.z}, cv[3] = {vel.x, vel.y, vel.z};
-    Real tt[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const Real pe = tp[k] - cp[k], ve = tv[k] - cv[k];
-        pos_e[k] = pe;
-        Real ip = clip_(ctl[3 + k] + pe * K.dt, Real(-2), Real(2));
-        if (k == 2) ip = clip_(ip, Real(-0.15), Real(0.15));
-        ctl[3 + k] = ip;
-        tt[k] = K.p_for[k] * pe + K.i_for[k] * ip + K.d_for[k] * ve;
-    }
-    tt[2] += K.grav;
-    Real sc = tt[0] * R.a02 + tt[1] * R.a12 + tt[2] * R.a22;
-    sc = sc < Real(0) ? Real(0) : sc;
-    const Real thrust = (sqrt_(sc * K.inv4kf) - K.rpm_const) * K.inv_scale;
-    const V3<Real> ttv = v3(tt[0], tt[1], tt[2]);
-    const V3<Real> zax = rsqrt_(dot(ttv, ttv)) * ttv;
-    Real sy, cy;
-    sincos_(tyaw, &sy, &cy);
-    const V3<Real> yc = cross(zax, v3(cy, sy, Real(0)));
-    const V3<Real> yax = rsqrt_(dot(yc, yc)) * yc;
-    const V3<Real> xax = cross(yax, zax);
+    Real thrust, tq[3], tt[3];
+    V3<Real> xax, yax;
+    dslpid_core<Real>(K, K.dt, K.hz, K.grav, K.inv4kf, K.rpm_const, K.inv_scale, R, rpy, pos, vel, tp, tyaw, tv, rates, ctl,
+                      thrust, tq, pos_e, tt, xax, yax);
     if (want_yaw_e) yaw_e = yaw_error<Real>(tt, tyaw, q, xax, yax, rpy.z);   // (wave-uniform: the caller's pointer)
-    // _dslPIDAttitudeControl (:212-259): rot_e = vee(Rt^T R - R^T Rt)
-    const V3<Real> c0 = v3(R.a00, R.a10, R.a20), c1 = v3(R.a01, R.a11, R.a21), c2 = v3(R.a02, R.a12, R.a22);
-    const Real rot_e[3] = {dot(zax, c1) - dot(c2, yax), dot(xax, c2) - dot(c0, zax), dot(yax, c0) - dot(c1, xax)};
-    const Real cur[3] = {rpy.x, rpy.y, rpy.z};
-    Real tq[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const Real rr_e = rates[k] - (cur[k] - ctl[k]) * K.hz;
-        ctl[k] = cur[k];
-        Real ir = clip_(ctl[6 + k] - rot_e[k] * K.dt, Real(-1500), Real(1500));
-        if (k < 2) ir = clip_(ir, Real(-1), Real(1));
-        ctl[6 + k] = ir;
-        tq[k] = clip_(-K.p_tor[k] * rot_e[k] + K.d_tor[k] * rr_e + K.i_tor[k] * ir, Real(-3200), Real(3200));
-    }
     // pwm = thrust + MIXER_MATRIX . torques, clipped, PWM -> RPM
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

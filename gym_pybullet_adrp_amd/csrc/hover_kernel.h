@@ -42,6 +42,7 @@
 #pragma once
 
 #include "adrp_device.h"
+#include "dslpid_core.h"
 
 namespace adrp {
 
@@ -616,49 +617,15 @@ __device__ __forceinline__ void dslpid_rpm(const HoverConst<Real>& C, const Body
     } else {   // ONE_D_PID: target_pos = pos + 0.1*[0, 0, a]
         tp = v3(b.pos.x, b.pos.y, b.pos.z + Real(0.1) * Real(act[0]));
     }
-    // _dslPIDPositionControl (:149-208)
-    constexpr Real PF[3] = {Real(.4), Real(.4), Real(1.25)}, IF[3] = {Real(.05), Real(.05), Real(.05)},
-                   DF[3] = {Real(.2), Real(.2), Real(.5)};
-    const Real pe[3] = {tp.x - b.pos.x, tp.y - b.pos.y, tp.z - b.pos.z};
-    const Real ve[3] = {tv.x - b.vel.x, tv.y - b.vel.y, tv.z - b.vel.z};
-    Real tt[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        Real ip = ctl[3 + k] + pe[k] * C.ctrl_dt;
-        ip = ip < Real(-2) ? Real(-2) : (ip > Real(2) ? Real(2) : ip);
-        if (k == 2) ip = ip < Real(-0.15) ? Real(-0.15) : (ip > Real(0.15) ? Real(0.15) : ip);
-        ctl[3 + k] = ip;
-        tt[k] = PF[k] * pe[k] + IF[k] * ip + DF[k] * ve[k];
-    }
-    tt[2] += C.pid_grav;
-    Real sc = tt[0] * R.a02 + tt[1] * R.a12 + tt[2] * R.a22;
-    sc = sc < Real(0) ? Real(0) : sc;
-    const Real thrust = (sqrt_(sc * C.pid_inv4kf) - Real(4070.3)) * Real(1.0 / 0.2685);
-    const V3<Real> ttv = v3(tt[0], tt[1], tt[2]);
-    const V3<Real> zax = rsqrt_(dot(ttv, ttv)) * ttv;
-    Real sy, cy;
-    sincos_(tyaw, &sy, &cy);
-    const V3<Real> yc = cross(zax, v3(cy, sy, Real(0)));
-    const V3<Real> yax = rsqrt_(dot(yc, yc)) * yc;
-    const V3<Real> xax = cross(yax, zax);
-    // _dslPIDAttitudeControl (:212-259): rot_e = vee(Rt^T R - R^T Rt)
-    const V3<Real> c0 = v3(R.a00, R.a10, R.a20), c1 = v3(R.a01, R.a11, R.a21), c2 = v3(R.a02, R.a12, R.a22);
-    const Real rot_e[3] = {dot(zax, c1) - dot(c2, yax), dot(xax, c2) - dot(c0, zax), dot(yax, c0) - dot(c1, xax)};
-    const Real cur[3] = {rpy.x, rpy.y, rpy.z};
-    constexpr Real PT[3] = {Real(70000), Real(70000), Real(60000)}, IT[3] = {Real(0), Real(0), Real(500)},
-                   DT[3] = {Real(20000), Real(20000), Real(12000)};
-    Real tq[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const Real rr_e = -(cur[k] - ctl[k]) * C.ctrl_hz;
-        ctl[k] = cur[k];
-        Real ir = ctl[6 + k] - rot_e[k] * C.ctrl_dt;
-        ir = ir < Real(-1500) ? Real(-1500) : (ir > Real(1500) ? Real(1500) : ir);
-        if (k < 2) ir = ir < Real(-1) ? Real(-1) : (ir > Real(1) ? Real(1) : ir);
-        ctl[6 + k] = ir;
-        const Real t = -PT[k] * rot_e[k] + DT[k] * rr_e + IT[k] * ir;
-        tq[k] = t < Real(-3200) ? Real(-3200) : (t > Real(3200) ? Real(3200) : t);
-    }
+    // the two loops (dslpid_core.h) with DSLPIDControl's CF2X gains (:42-47) and no target rates
+    constexpr DslpidGains<Real> K = {{Real(.4), Real(.4), Real(1.25)}, {Real(.05), Real(.05), Real(.05)},
+                                     {Real(.2), Real(.2), Real(.5)}, {Real(70000), Real(70000), Real(60000)},
+                                     {Real(0), Real(0), Real(500)}, {Real(20000), Real(20000), Real(12000)}};
+    const Real tpa[3] = {tp.x, tp.y, tp.z}, tva[3] = {tv.x, tv.y, tv.z}, rates[3] = {Real(0), Real(0), Real(0)};
+    Real thrust, tq[3], pos_e[3], tt[3];
+    V3<Real> xax, yax;
+    dslpid_core<Real>(K, C.ctrl_dt, C.ctrl_hz, C.pid_grav, C.pid_inv4kf, Real(4070.3), Real(1.0 / 0.2685), R, rpy, b.pos,
+                      b.vel, tpa, tyaw, tva, rates, ctl, thrust, tq, pos_e, tt, xax, yax);
     // CF2X mixer [[-.5,-.5,-1],[-.5,.5,1],[.5,.5,-1],[.5,-.5,1]], PWM clip, PWM -> RPM
     const Real hr = Real(0.5) * tq[0], hp = Real(0.5) * tq[1];
     const Real pwm[4] = {thrust - hr - hp - tq[2], thrust - hr + hp + tq[2], thrust + hr + hp - tq[2],

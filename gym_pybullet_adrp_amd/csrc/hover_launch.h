@@ -7,20 +7,14 @@
 // launch dispatch
 // ---------------------------------------------------------------------------------------------
 
-// launch with optional start/stop events recorded by the dispatch itself
+// the step kernels take the hot pointers as arguments of their own and the rest as a HoverTail
 template <typename K, typename Real>
 static void launch(K kernel, dim3 grid, dim3 blk, hipStream_t s, const HoverArgs<Real>& a, adrp_t* h) {
     HoverTail<Real> t;
     memset(&t, 0, sizeof t);
     t.c = a.c; t.r = a.r; t.term = a.term; t.trunc = a.trunc; t.tobs = a.tobs; t.contact_count = a.contact_count;
     t.seed = a.seed; t.env_offset = a.env_offset; t.B = a.B; t.D = a.D; t.autoreset = a.autoreset;
-    if (h->prof_n < h->prof_cap) {
-        hipExtLaunchKernelGGL(kernel, grid, blk, 0, s, h->ev_start[h->prof_n], h->ev_stop[h->prof_n], 0,
-                              a.f, a.ring, a.ist, a.act, a.obs, a.rew, a.E, t);
-        ++h->prof_n;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, blk, 0, s, a.f, a.ring, a.ist, a.act, a.obs, a.rew, a.E, t);
-    }
+    launch_profiled(h, kernel, grid, blk, s, a.f, a.ring, a.ist, a.act, a.obs, a.rew, a.E, t);
 }
 
 template <typename Real, int A, int B, bool DEF, bool STG = false, int CTL = 0, bool HELP = false>

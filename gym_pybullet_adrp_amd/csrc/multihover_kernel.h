@@ -8,12 +8,9 @@
 //   _preprocessAction (RPM, ONE_D_RPM), _computeObs                    envs/BaseRLAviary.py:160-239, 284-319
 //   TARGET_POS, _computeReward / _computeTerminated / _computeTruncated  envs/MultiHoverAviary.py:71-130
 //
-// Lane mapping: the N drones of env e are lanes [e G, e G + N) of the grid, G = the next power of
-// two >= N, so a group is aligned and never straddles a wave (64 / G envs per wave).  Lanes n >= N of
-// a group and groups past E are inactive: they run the same instruction stream on a benign state (the
-// cross-lane moves below need every lane of the wave in step), load nothing, store nothing, and every
-// exchange or reduction masks them out by k < N.  A live lane only ever reads lanes of its own group,
-// so an env's results do not depend on E or on where the env sits in the batch.
+// Lane mapping and inactive lanes: lane_group.h's header comment; the group moves and the downwash are
+// its functions (shared with ctrl_kernel.h).  A live lane only ever reads lanes of its own group, so an
+// env's results do not depend on E or on where the env sits in the batch.
 //
 // The sub-step body is hover_kernel.h's (pyb_chain / pyb_substep / dyn_substep); the downwash enters it
 // as one more world-frame force (pyb_substep's Fext).  State, ints and ring use HoverAviary's layout
@@ -21,8 +18,7 @@
 #pragma once
 
 #include "hover_kernel.h"
-#include "race_kernel.h"   // grp_bcast: DPP quad_perm (G <= 4) / ds_bpermute (G = 8) group broadcast (the reductions)
-#include "race_quad.h"     // dw_exp
+#include "lane_group.h"
 
 namespace adrp {
 
@@ -35,33 +31,12 @@ struct MultiConst {
     Real target[ADRP_MAX_DRONES][3];            // INIT_XYZS[n] + (0, 0, 1 / (n + 1))
 };
 
-constexpr int mh_group(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8; }
-
-// value of lane (n + r) mod G of this lane's group of G adjacent lanes, n the lane's place in the group,
-// 0 < r < G.  G <= 4: one DPP quad_perm move (a rotation of the quad, or of its halves); G = 8:
-// ds_bpermute.  r must fold to a constant (unrolled loops).
-template <int G>
-__device__ __forceinline__ int grp_rot_i(int v, int r, int n) {
-    if constexpr (G == 2) {
-        return __builtin_amdgcn_mov_dpp(v, 0xb1, 0xf, 0xf, false);   // quad_perm [1, 0, 3, 2]
-    } else if constexpr (G == 4) {
-        switch (r) {
-            case 1: return __builtin_amdgcn_mov_dpp(v, 0x39, 0xf, 0xf, false);    // [1, 2, 3, 0]
-            case 2: return __builtin_amdgcn_mov_dpp(v, 0x4e, 0xf, 0xf, false);    // [2, 3, 0, 1]
-            default: return __builtin_amdgcn_mov_dpp(v, 0x93, 0xf, 0xf, false);   // [3, 0, 1, 2]
-        }
-    } else {
-        return __shfl(v, (n + r) & (G - 1), G);
-    }
-}
-template <int G>
-__device__ __forceinline__ float grp_rot(float v, int r, int n) {
-    return __int_as_float(grp_rot_i<G>(__float_as_int(v), r, n));
-}
-template <int G>
-__device__ __forceinline__ double grp_rot(double v, int r, int n) {   // a 64-bit value goes as two 32-bit moves
-    const int lo = grp_rot_i<G>(__double2loint(v), r, n), hi = grp_rot_i<G>(__double2hiint(v), r, n);
-    return __hiloint2double(hi, lo);
+// the column view of the [..][E N] state for load_body / store_body
+template <typename Real>
+__device__ __forceinline__ HoverArgs<Real> mh_columns(const HoverArgs<Real>& a, size_t EN) {
+    HoverArgs<Real> ac = a;
+    ac.E = int(EN);
+    return ac;
 }
 
 // BaseAviary.reset of drone n of env e: HoverAviary's draw on the drone's own Philox stream
@@ -108,15 +83,16 @@ __global__ void __launch_bounds__(kStepBlock) multihover_step_kernel(HoverArgs<R
     const HoverConst<Real>& C = *a.c;
     const MultiConst<Real>& M = *mp;
     constexpr int BR = B > 0 ? B : 1;
-    const int N = M.N, E = a.E, BB = B > 0 ? B : a.B, D = B > 0 ? 12 + B * A : a.D;
+    const int N = M.N, BB = B > 0 ? B : a.B, D = B > 0 ? 12 + B * A : a.D;
+    // (spelled out in both grouped step kernels: behind a shared lane descriptor they measured 0.04-0.12 us slower)
+    const int E = a.E;
     const long long t = (long long)blockIdx.x * kStepBlock + threadIdx.x;
     const long long eg = t / G;
     const int n = int(t % G);
     const bool live = eg < E && n < N;
     const int e = live ? int(eg) : 0;
     const size_t EN = size_t(E) * N, col = size_t(e) * N + n;   // (col is only used by live lanes)
-    HoverArgs<Real> ac = a;   // the column view of the state for load_body / store_body
-    ac.E = int(EN);
+    const HoverArgs<Real> ac = mh_columns(a, EN);
     // ---- loads (live lanes); inactive lanes hover at rest one metre up ----
     float act[A];
 #pragma unroll
@@ -128,7 +104,7 @@ __global__ void __launch_bounds__(kStepBlock) multihover_step_kernel(HoverArgs<R
         for (int j = 0; j < A; ++j) ring[p][j] = 0.0f;
     int32_t sc = 0, ep = 0, head = 0;
     const bool lag = C.link_lag && !DYN;
-    Body<Real> b;
+    Body<Real> b;   // (spelled out too: behind a function call the float64 PYB_DRAG G = 8 kernel takes two more AGPRs)
     b.pos = v3(Real(0), Real(0), Real(1));
     b.q = {Real(0), Real(0), Real(0), Real(1)};
     b.ql = b.q;
@@ -173,31 +149,7 @@ __global__ void __launch_bounds__(kStepBlock) multihover_step_kernel(HoverArgs<R
     if constexpr (DYN) {
         for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
     } else if constexpr (DW) {
-        // _downwash (BaseAviary.py:792-818), every sub-step from the group's current positions (:350-351
-        // refreshes self.pos per sub-step in these modes).  Lane n takes its partners in the order n + 1,
-        // n + 2, ... (mod G): G - 1 terms, none for itself, and an order that depends on the drone's place in
-        // its env alone, not on E or on the env's place in the batch.  A term is
-        // alpha exp(-(dxy / beta)^2 / 2) with alpha = DW1 (PROP_RADIUS / (4 dz))^2, beta = DW2 dz + DW3;
-        // only dxy^2 enters, so no square root.  The force acts on link 4 along the z axis of the cached
-        // link basis (the current one once _groundEffect's getLinkStates has refreshed it), through the
-        // centre of mass: no torque.  N = 1 (G = 1) has no partner and no exchange.
-        const Real dw1 = M.dw1, dw2 = M.dw2, dw3 = M.dw3, prop_r = M.prop_r;
-        auto downwash = [&](const Body<Real>& bb, const Chain<Real>& st) {
-            Real tsum = Real(0);
-#pragma unroll
-            for (int r = 1; r < G; ++r) {
-                const int k = (n + r) & (G - 1);
-                const Real ox = grp_rot<G>(bb.pos.x, r, n), oy = grp_rot<G>(bb.pos.y, r, n), oz = grp_rot<G>(bb.pos.z, r, n);
-                const Real dz = oz - bb.pos.z, dx = ox - bb.pos.x, dy = oy - bb.pos.y;
-                const Real dxy2 = dx * dx + dy * dy;
-                const Real kk = prop_r * rcp_nc_(Real(4) * dz);
-                const Real rb = rcp_nc_(dw2 * dz + dw3);
-                const Real term = dw1 * kk * kk * dw_exp(Real(-0.5) * (dxy2 * rb * rb), f64::kExp2Tab32);
-                tsum += (k < N && dz > Real(0) && dxy2 < Real(100)) ? term : Real(0);
-            }
-            const V3<Real> z = GND ? st.zc : st.zs;
-            return v3(-tsum * z.x, -tsum * z.y, -tsum * z.z);
-        };
+        const Downwash<Real, G, GND> downwash = {M.dw1, M.dw2, M.dw3, M.prop_r, n, N};
         touched = pyb_chain<Real, PH, 0, DRAG>(C, b, rpm, lag, downwash);
     } else {
         touched = pyb_chain<Real, PH, 0, DRAG>(C, b, rpm, lag, NoExtForce{});
@@ -269,29 +221,38 @@ __global__ void __launch_bounds__(kStepBlock) multihover_step_kernel(HoverArgs<R
     a.ist[HI_RING_HEAD * EN + col] = head1;
 }
 
-// reset kernel (BaseAviary.reset -> _housekeeping -> _computeObs), one lane per column; the ring of a
-// reset env is cleared
-template <typename Real, int A>
-__global__ void __launch_bounds__(256) multihover_reset_kernel(HoverArgs<Real> a, const MultiConst<Real>* mp) {
-    const MultiConst<Real>& M = *mp;
-    const size_t EN = size_t(a.E) * M.N;
-    const size_t col = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (col >= EN) return;
+// What the reset kernels of the [..][E N] column layouts share (BaseAviary.reset -> _housekeeping ->
+// _computeObs), one lane per column: the drone's new state drawn and stored, the env's step counter and
+// episode, and the first twelve obs values.  False for a lane past the last column or of an env the mask
+// leaves alone.  rpm_always: last_rpm_* is stored in every physics mode (the state-row envs), not only
+// with drag.
+template <typename Real>
+__device__ __forceinline__ bool mh_reset_column(const HoverArgs<Real>& a, const MultiConst<Real>& M, bool rpm_always,
+                                                size_t& EN, size_t& col, Body<Real>& b, float o12[12]) {
+    EN = size_t(a.E) * M.N;
+    col = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (col >= EN) return false;
     const int e = int(col / M.N), n = int(col % M.N);
-    if (a.mask && !a.mask[e]) return;
+    if (a.mask && !a.mask[e]) return false;
     const HoverConst<Real>& C = *a.c;
     const bool dyn = C.physics == ADRP_PHYS_DYN;
-    const bool drag = C.physics == ADRP_PHYS_PYB_DRAG || C.physics == ADRP_PHYS_PYB_GND_DRAG_DW;
-    HoverArgs<Real> ac = a;
-    ac.E = int(EN);
-    Body<Real> b;
+    const bool drag = rpm_always || C.physics == ADRP_PHYS_PYB_DRAG || C.physics == ADRP_PHYS_PYB_GND_DRAG_DW;
     int32_t sc = 0, ep = a.ist[HI_EPISODE * EN + col];   // (replicated on the env's columns: the lane's own copy)
     mh_reset_state(a, C, M, e, n, b, sc, ep);
-    store_body(ac, int(col), b, C.link_lag && !dyn, drag, dyn);
+    store_body(mh_columns(a, EN), int(col), b, C.link_lag && !dyn, drag, dyn);
     a.ist[HI_STEP * EN + col] = sc;
     a.ist[HI_EPISODE * EN + col] = ep;
-    float o12[12];
     hover_obs12(C, b, o12);
+    return true;
+}
+
+// reset kernel, one lane per column; the ring of a reset env is cleared
+template <typename Real, int A>
+__global__ void __launch_bounds__(256) multihover_reset_kernel(HoverArgs<Real> a, const MultiConst<Real>* mp) {
+    size_t EN, col;
+    Body<Real> b;
+    float o12[12];
+    if (!mh_reset_column(a, *mp, false, EN, col, b, o12)) return;
     mh_clear_ring<A>(a.ring, a.B, EN, col);
     mh_write_row_cleared(a.obs + col * size_t(a.D), o12, a.D);
 }

@@ -15,6 +15,7 @@
 #include "../../include/adrp.h"
 #include "adrp_device.h"
 #include "commander.h"
+#include "lane_group.h"   // grp_bcast: the group broadcast
 
 namespace adrp {
 
@@ -217,39 +218,6 @@ __device__ __forceinline__ float degf_(float r) { return (180.0f / 3.14159265358
 
 template <typename Real>
 __device__ __forceinline__ Real shfl_(Real v, int src, int width) { return __shfl(v, src, width); }
-
-// value of lane k of this lane's group of G adjacent lanes (the drones of one env).  G <= 4: a
-// DPP quad_perm move (one VALU op, no LDS round trip); G = 8: ds_bpermute.  k must fold to a
-// constant (unrolled loops).
-template <int G>
-__device__ __forceinline__ int grp_bcast_i(int v, int k) {
-    if constexpr (G == 1) {
-        return v;
-    } else if constexpr (G == 2) {
-        switch (k) {   // quad_perm [k, k, 2 + k, 2 + k]
-            case 0: return __builtin_amdgcn_mov_dpp(v, 0 | (0 << 2) | (2 << 4) | (2 << 6), 0xf, 0xf, false);
-            default: return __builtin_amdgcn_mov_dpp(v, 1 | (1 << 2) | (3 << 4) | (3 << 6), 0xf, 0xf, false);
-        }
-    } else if constexpr (G == 4) {
-        switch (k) {   // quad_perm [k, k, k, k]
-            case 0: return __builtin_amdgcn_mov_dpp(v, 0x00, 0xf, 0xf, false);
-            case 1: return __builtin_amdgcn_mov_dpp(v, 0x55, 0xf, 0xf, false);
-            case 2: return __builtin_amdgcn_mov_dpp(v, 0xaa, 0xf, 0xf, false);
-            default: return __builtin_amdgcn_mov_dpp(v, 0xff, 0xf, 0xf, false);
-        }
-    } else {
-        return __shfl(v, k, G);
-    }
-}
-template <int G>
-__device__ __forceinline__ float grp_bcast(float v, int k) {
-    return __int_as_float(grp_bcast_i<G>(__float_as_int(v), k));
-}
-template <int G>
-__device__ __forceinline__ double grp_bcast(double v, int k) {
-    const int lo = grp_bcast_i<G>(__double2loint(v), k), hi = grp_bcast_i<G>(__double2hiint(v), k);
-    return __hiloint2double(hi, lo);
-}
 
 // ---------------------------------------------------------------------------------------
 // geometry: URDF collision shapes, GJK distance, ray vs cylinder

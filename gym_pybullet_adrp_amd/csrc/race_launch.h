@@ -13,14 +13,7 @@ template <typename Real, int PH>
 static void launch_race_q4(const RaceArgs<Real>& a, int G, hipStream_t s, adrp_t* h) {
     const bool draws = h->cfg.track.disturbances;   // (race_quad_ok: then drawn up front)
     const dim3 blk(kRaceBlock), grid((unsigned)((size_t(h->E) * G * 4 + kRaceBlock - 1) / kRaceBlock));
-    auto go = [&](auto kernel) {
-        if (h->prof_n < h->prof_cap) {
-            hipExtLaunchKernelGGL(kernel, grid, blk, 0, s, h->ev_start[h->prof_n], h->ev_stop[h->prof_n], 0, a);
-            ++h->prof_n;
-        } else {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, s, a);
-        }
-    };
+    auto go = [&](auto kernel) { launch_profiled(h, kernel, grid, blk, s, a); };
     auto by_g = [&](auto dr) {
         constexpr bool D = decltype(dr)::value;
         switch (G) {
@@ -42,13 +35,7 @@ static void launch_race_q4(const RaceArgs<Real>& a, int G, hipStream_t s, adrp_t
 template <typename Real, int PH>
 static void launch_race_cmd(const RaceArgs<Real>& a, hipStream_t s, adrp_t* h) {
     const dim3 blk(kRaceBlock), grid((unsigned)((size_t(h->E) * 8 + kRaceBlock - 1) / kRaceBlock));
-    auto kernel = race_step_kernel<Real, PH, 8, 0, true>;
-    if (h->prof_n < h->prof_cap) {
-        hipExtLaunchKernelGGL(kernel, grid, blk, 0, s, h->ev_start[h->prof_n], h->ev_stop[h->prof_n], 0, a);
-        ++h->prof_n;
-    } else {
-        hipLaunchKernelGGL(kernel, grid, blk, 0, s, a);
-    }
+    launch_profiled(h, race_step_kernel<Real, PH, 8, 0, true>, grid, blk, s, a);
 }
 
 template <typename Real, int PH>
@@ -63,14 +50,7 @@ static void launch_race_g(const RaceArgs<Real>& a, int G, hipStream_t s, adrp_t*
                         : h->cfg.track.disturbances && h->S <= kRacePreS ? 2 : 1;
     const dim3 blk(kRaceBlock * (helpers ? 1 + kRaceHelpers : 1)),
         grid((unsigned)((size_t(h->E) * G + kRaceBlock - 1) / kRaceBlock));
-    auto go = [&](auto kernel) {
-        if (h->prof_n < h->prof_cap) {
-            hipExtLaunchKernelGGL(kernel, grid, blk, 0, s, h->ev_start[h->prof_n], h->ev_stop[h->prof_n], 0, a);
-            ++h->prof_n;
-        } else {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, s, a);
-        }
-    };
+    auto go = [&](auto kernel) { launch_profiled(h, kernel, grid, blk, s, a); };
     constexpr bool F32 = sizeof(Real) == 4;
     auto by_g = [&](auto pre) {
         constexpr int P = decltype(pre)::value;

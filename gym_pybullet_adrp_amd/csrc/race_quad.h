@@ -26,15 +26,12 @@
 
 #include <type_traits>
 
+#include "lane_group.h"   // dw_exp
 #include "race_kernel.h"
 
 namespace adrp {
 
 constexpr int kQuadDrones = kRaceBlock / 4;   // drones per 64-lane block
-
-// the downwash exponential: fp32 v_exp_f32; fp64 the table form (x <= 0)
-__device__ __forceinline__ float dw_exp(float x, const double*) { return fexp_(x); }
-__device__ __forceinline__ double dw_exp(double x, const double* tab) { return f64::exp_tab(x, tab); }
 
 // DPP quad moves (one VALU op): value of quad lane k (k must fold to a constant), and the mirror
 // lane 3 - ql

@@ -18,9 +18,9 @@ import torch
 
 from .. import _lib
 from ..utils import abi
-from ..utils.enums import ActionType, DroneModel, ObservationType, Physics, PHYSICS_CODE
+from ..utils.enums import ActionType, DroneModel, ObservationType, Physics
 from ..utils.spaces import Box
-from .base import AviaryEnv
+from .kin import KinAviary
 
 
 # ActionType -> C-ABI code, and the per-drone action width (BaseRLAviary.py:141-147).  PID /
@@ -32,78 +32,33 @@ _ACT_SIZE = {ActionType.RPM: 4, ActionType.VEL: 4, ActionType.PID: 3, ActionType
              ActionType.ONE_D_PID: 1}
 
 
-class HoverAviary(AviaryEnv):
+class HoverAviary(KinAviary):
     """Batched counterpart of gym_pybullet_adrp.envs.HoverAviary."""
+
+    TASK = abi.TASK_HOVER
 
     def __init__(self, drone_model: DroneModel = DroneModel.CF2X, initial_xyzs=None, initial_rpys=None,
                  physics: Physics = Physics.PYB, pyb_freq: int = 240, ctrl_freq: int = 30, gui=False,
                  record=False, obs: ObservationType = ObservationType.KIN, act: ActionType = ActionType.RPM,
                  *, num_envs: int = 1, device: int = 0, precision: str = "fp64", seed: int = 0,
                  autoreset: bool = True, init_noise=None, env_offset: int = 0, link_frame_lag: bool = True):
-        if drone_model != DroneModel.CF2X:
-            raise ValueError("only DroneModel.CF2X (cf2x_IROS.urdf) is supported")
-        if gui or record:
-            raise ValueError("GUI / video recording are out of scope (DESIGN.md)")
+        super().__init__(drone_model, None, None, initial_xyzs, initial_rpys, physics, pyb_freq, ctrl_freq, gui, record,
+                         obs, act, num_envs=num_envs, device=device, precision=precision, seed=seed, autoreset=autoreset,
+                         init_noise=init_noise, env_offset=env_offset, link_frame_lag=link_frame_lag)
+        self._act_ok = (None, 0)        # (tensor, address) of the last validated action
+
+    def _check_types(self, obs, act):
         if obs != ObservationType.KIN:
             raise ValueError("only ObservationType.KIN is supported")
         if act not in _ACT_CODE:
             raise ValueError("supported action types: RPM, ONE_D_RPM, PID, VEL, ONE_D_PID")
-        if pyb_freq % ctrl_freq != 0:
-            raise ValueError("[ERROR] in BaseAviary.__init__(), pyb_freq is not divisible by env_freq.")
-        cfg = _lib.default_config(abi.TASK_HOVER)
-        cfg.physics = PHYSICS_CODE[physics]
-        cfg.act_type = _ACT_CODE[act]
-        cfg.num_envs = int(num_envs)
-        cfg.pyb_freq, cfg.ctrl_freq = int(pyb_freq), int(ctrl_freq)
-        cfg.action_buffer_size = int(ctrl_freq // 2)
-        cfg.autoreset = 1 if autoreset else 0
-        cfg.precision = {"fp32": 0, "fp64": 1}[precision]
-        cfg.link_frame_lag = 1 if link_frame_lag else 0
-        cfg.seed = int(seed) & (2 ** 64 - 1)
-        cfg.env_offset = int(env_offset)
-        if initial_xyzs is not None:
-            abi.set_vec(cfg.init_xyz[0], np.asarray(initial_xyzs, float).reshape(3))
-        if initial_rpys is not None:
-            abi.set_vec(cfg.init_rpy[0], np.asarray(initial_rpys, float).reshape(3))
-        for key, dst in (("xyz", cfg.init_xyz_noise), ("rpy", cfg.init_rpy_noise), ("vel", cfg.init_vel_noise),
-                         ("omega", cfg.init_omega_noise)):
-            if init_noise and key in init_noise:
-                abi.set_vec(dst, np.broadcast_to(np.asarray(init_noise[key], float), 3))
-        self.cfg = cfg
-        self.h = _lib.Handle(cfg, device)
-        self.device = self.h.device
-        # reference attributes
-        self.DRONE_MODEL, self.PHYSICS, self.OBS_TYPE, self.ACT_TYPE = drone_model, physics, obs, act
-        self.NUM_DRONES = 1
-        self.PYB_FREQ, self.CTRL_FREQ = int(pyb_freq), int(ctrl_freq)
-        self.PYB_STEPS_PER_CTRL = self.PYB_FREQ // self.CTRL_FREQ
-        self.PYB_TIMESTEP, self.CTRL_TIMESTEP = 1.0 / self.PYB_FREQ, 1.0 / self.CTRL_FREQ
-        self.ACTION_BUFFER_SIZE = int(ctrl_freq // 2)
+        return _ACT_CODE[act]
+
+    def _task_attributes(self, d):
         self.TARGET_POS = np.array([0, 0, 1])
         self.EPISODE_LEN_SEC = 8
-        d = cfg.drone
-        self.M, self.L, self.KF, self.KM = d.m, d.l, d.kf, d.km
-        self.J = np.diag([d.ixx, d.iyy, d.izz])
-        self.G = cfg.gravity
-        self.GRAVITY = self.G * self.M
-        self.HOVER_RPM = np.sqrt(self.GRAVITY / (4 * self.KF))
-        self.MAX_RPM = np.sqrt((d.thrust2weight * self.GRAVITY) / (4 * self.KF))
-        if act == ActionType.VEL:
+        if self.ACT_TYPE == ActionType.VEL:
             self.SPEED_LIMIT = 0.03 * d.max_speed_kmh * (1000 / 3600)   # BaseRLAviary.py:94-95
-        self.num_envs = cfg.num_envs
-        self.action_space = self._actionSpace()
-        self.observation_space = self._observationSpace()
-        E, D = self.num_envs, self.h.D
-        self._obs = torch.zeros((E, 1, D), dtype=torch.float32, device=self.device)
-        self._tobs = torch.zeros_like(self._obs)
-        self._rew = torch.zeros(E, dtype=torch.float32, device=self.device)
-        # the kernel writes 0/1 bytes: valid torch.bool storage, returned without a cast
-        self._term = torch.zeros(E, dtype=torch.bool, device=self.device)
-        self._trunc = torch.zeros(E, dtype=torch.bool, device=self.device)
-        self._act_shape = (E, 1, self.h.A)
-        self._info = {"answer": 42, "terminal_observation": self._tobs}
-        self.h.bind(self._obs, self._rew, self._term, self._trunc, self._tobs)
-        self._act_ok = (None, 0)        # (tensor, address) of the last validated action
 
     # ---- spaces (BaseRLAviary.py:132-156, 243-277) ----
     def _actionSpace(self):
@@ -119,22 +74,7 @@ class HoverAviary(AviaryEnv):
         high += [+1] * size * self.ACTION_BUFFER_SIZE
         return Box(low=np.array([low]), high=np.array([high]), dtype=np.float32)
 
-    # ---- gymnasium-style API, batched ----
-    def reset(self, seed: int = None, options: dict = None, mask=None):
-        """Reset all envs (or those with mask[e] != 0); `seed` re-keys the random streams first.
-        Returns (obs [E,1,D], info)."""
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-        if seed is not None:
-            # BaseAviary.reset(seed) reseeds np_random, then resets: here the Philox key of every env
-            # (a fresh env built with this seed gives the same episodes from here on)
-            if m is not None:
-                raise ValueError("reset(seed=...) re-keys every env: call it without a mask")
-            self.h.reseed(seed)
-        self.h.reset(self._obs, m)
-        return self._obs, {"answer": 42}
-
+    # ---- gymnasium-style API, batched (reset, bind_outputs: KinAviary) ----
     def step(self, action):
         """One env.step of every env: action [E,1,A] (torch or numpy, in [-1,1]).
 
@@ -154,26 +94,6 @@ class HoverAviary(AviaryEnv):
         self.h.step_ptr(act.data_ptr())
         return self._obs, self._rew, self._term, self._trunc, self._info
 
-    def close(self):
-        self.h.close()
-
-    def bind_outputs(self, obs, rew, term, trunc, tobs=None):
-        """Write step / reset outputs into caller-owned device tensors from now on (e.g. views of a
-        collective's send buffer, sharding.ShardedAviary(packed=True), or the SB3 adapter's packed
-        host-copy buffer): obs [E,N,D] float32, reward [E] float32, terminated / truncated [E] bool,
-        optionally the terminal observations [E,N,D] float32, all contiguous on this env's device."""
-        want = ((self._obs, obs), (self._rew, rew), (self._term, term), (self._trunc, trunc))
-        if tobs is not None:
-            want += ((self._tobs, tobs),)
-        for old, new in want:
-            if new.shape != old.shape or new.dtype != old.dtype or new.device != old.device or not new.is_contiguous():
-                raise ValueError(f"bind_outputs: need a contiguous {old.dtype} {tuple(old.shape)} tensor on {old.device}")
-        self._obs, self._rew, self._term, self._trunc = obs, rew, term, trunc
-        if tobs is not None:
-            self._tobs = tobs
-            self._info["terminal_observation"] = tobs
-        self.h.bind(self._obs, self._rew, self._term, self._trunc, self._tobs)
-
     # ---- persistent stepping (BASELINE config 1: a Python loop stepping a few envs synchronously) ----
     def persistent(self):
         """A resident step kernel for this env (include/adrp.h adrp_persistent_*): ``step(action)``
@@ -181,24 +101,6 @@ class HoverAviary(AviaryEnv):
         step.  Use as a context manager; ``step`` / ``reset`` / ``get_state`` of the env itself are
         refused until it is closed."""
         return PersistentStepper(self)
-
-    # ---- introspection (tests / teacher forcing) ----
-    def get_state(self):
-        return self.h.get_state()
-
-    def set_state(self, f, i):
-        self.h.set_state(f, i)
-
-    def state_field_names(self):
-        return self.h.field_names()
-
-    def step_bytes(self):
-        return self.h.step_bytes()
-
-    @property
-    def kernel_name(self):
-        """the step-kernel instantiation this env launches now (include/adrp.h adrp_handle_kernel_name)"""
-        return self.h.kernel_name()
 
 
 class PersistentStepper:

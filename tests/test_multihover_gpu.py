@@ -321,11 +321,13 @@ def stacked_state(rng, env, equal_z=True, vel=0.5, beta_margin=0.02):
 
 
 @pytest.mark.parametrize("precision", ["fp64", "fp32"])
-@pytest.mark.parametrize("N", [3, 8])
+@pytest.mark.parametrize("N", [3, 5, 8])
 @pytest.mark.parametrize("physics", DOWNWASH)
 def test_downwash_one_substep(physics, N, precision):
     """S = 1: the state after the step is the single-drone oracle's (no neighbour, no downwash) plus
-    dv = dt F / m, dp = dt dv, F the oracle's own force assembly of the N drones minus the drone's alone"""
+    dv = dt F / m, dp = dt dv, F the oracle's own force assembly of the N drones minus the drone's alone.
+    N = 5 is the smallest with the G = 8 ds_bpermute exchange, three inactive lanes per group and masked
+    partners that wrap around the group ((n + r) & 7)."""
     E, rtol = 32, RTOL[precision]
     rng = np.random.default_rng(400 + N + DOWNWASH.index(physics))
     env = MultiHoverAviary(num_drones=N, physics=physics, pyb_freq=240, ctrl_freq=240, num_envs=E,
