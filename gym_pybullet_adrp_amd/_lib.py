@@ -138,6 +138,8 @@ def load():
     lib.adrp_race_results_step.restype = I
     lib.adrp_race_results_step_env.argtypes = [P, P, P, P, P, P]
     lib.adrp_race_results_step_env.restype = I
+    lib.adrp_race_plan.argtypes = [P, P]
+    lib.adrp_race_plan.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]
     lib.adrp_dslpid_default_params.restype = I
     lib.adrp_dslpid_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]

@@ -11,19 +11,25 @@ predict(obs[i], ep_time=episode_step / ctrl_freq) once per env.step).  Per drone
     end one NOTIFY [ep_time], one LAND [0, 2], then NONE.
 CTRL_FREQ is the controller's own 25 Hz (utils/constants.py:31), not the env's ctrl_freq.
 
-The spline is planned on the host at construction / re-plan (scipy, once per distinct start);
-predict() is a handful of tensor ops on the env's device and returns (codes int32 [E, N],
-args float64 [E, N, 14]) for MultiRaceAviary.step((codes, args)) / adrp_race_command.
+The spline is planned at construction / re-plan: on the host by default (scipy, once per distinct
+start), or with planner="device" by one adrp_race_plan launch over the observation tensor in place
+(csrc/spline_plan.h, the same FITPACK fit).  predict() is a handful of tensor ops on
+the env's device and returns (codes int32 [E, N], args float64 [E, N, 14]) for
+MultiRaceAviary.step((codes, args)) / adrp_race_command.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from .commands import CMD_ARGS, COMMAND_CODE, TIME_SLOT
+from .utils import abi
 from .utils.enums import Command
 
 CTRL_FREQ = 25          # utils/constants.py:31-32 (the controller's clock)
 Z_LOW, Z_HIGH = 0.3, 0.775
 DURATION = 12           # s of spline (HardCodedController.py:112)
+PLANNERS = ("host", "device")
 TAKEOFF = (0.3, 2.0)    # height, duration (HardCodedController.py:160)
 LAND = (0.0, 2.0)       # HardCodedController.py:184
 
@@ -59,12 +65,24 @@ class HardCodedCommander:
     """One HardCodedController per drone of an [E, N] batch.
 
     obs0: the reset observation [E, N, D] (MultiRaceAviary.reset); delay: [N] or [E, N] seconds of
-    extra take-off wait (scripts/sim.py:75 uses the drone index, the default)."""
+    extra take-off wait (scripts/sim.py:75 uses the drone index, the default).
 
-    def __init__(self, obs0, delay=None, device=None):
-        o = obs0.detach().cpu().numpy() if isinstance(obs0, torch.Tensor) else np.asarray(obs0)
-        if o.ndim == 2:
-            o = o[None]
+    planner: "host" plans with scipy on the host; "device" plans every drone in one adrp_race_plan launch
+    on the observation tensor in place (a float32 tensor on a GPU; only one reduced status word is read
+    back per replan).  A drone whose device fit did not end with FITPACK's ier = 0 is re-planned on the
+    host and counted in ``host_fallbacks``."""
+
+    def __init__(self, obs0, delay=None, device=None, planner="host"):
+        if planner not in PLANNERS:
+            raise ValueError(f"planner must be one of {PLANNERS}, not {planner!r}")
+        self.planner = planner
+        self.host_fallbacks = 0
+        if planner == "device":
+            o = self._device_obs(obs0)
+        else:
+            o = obs0.detach().cpu().numpy() if isinstance(obs0, torch.Tensor) else np.asarray(obs0)
+            if o.ndim == 2:
+                o = o[None]
         self.E, self.N = o.shape[:2]
         self.device = torch.device(device) if device is not None else (
             obs0.device if isinstance(obs0, torch.Tensor) else torch.device("cpu"))
@@ -76,6 +94,8 @@ class HardCodedCommander:
         self._ref = torch.empty((self.E, self.N, self.L, 3), dtype=torch.float64, device=self.device)
         self._flags = torch.zeros((3, self.E, self.N), dtype=torch.bool, device=self.device)  # take_off, notify, land
         self._cache = {}
+        if planner == "device":
+            self._device_init()
         self.replan(o)
         dev = self.device
         self._codes = {c: torch.tensor(COMMAND_CODE[c], dtype=torch.int32, device=dev)
@@ -84,6 +104,8 @@ class HardCodedCommander:
     def replan(self, obs0, mask=None):
         """Rebuild the controllers of the envs with mask[e] (all if None) from their reset observation
         (scripts/sim.py:72-76 builds new agents every episode)."""
+        if self.planner == "device":
+            return self._replan_device(obs0, mask)
         o = obs0.detach().cpu().numpy() if isinstance(obs0, torch.Tensor) else np.asarray(obs0)
         if o.ndim == 2:
             o = o[None]
@@ -102,6 +124,67 @@ class HardCodedCommander:
         idx = torch.as_tensor(np.asarray(list(envs), np.int64), device=self.device)
         self._ref[idx] = torch.as_tensor(ref, device=self.device)
         self._flags[:, idx] = False
+
+    # ---- planner="device" ----
+    @staticmethod
+    def _device_obs(obs0):
+        if not (isinstance(obs0, torch.Tensor) and obs0.is_cuda and obs0.dtype == torch.float32):
+            raise ValueError('planner="device" plans from the observation tensor in place: a float32 tensor on a GPU')
+        return obs0[None] if obs0.dim() == 2 else obs0
+
+    def _device_init(self):
+        from . import _lib
+        if self.device.type != "cuda":
+            raise ValueError('planner="device" needs the commander on a GPU')
+        self.device = self._ref.device         # with its index, as the observation's device reads
+        self._lib = _lib
+        self._samples = torch.as_tensor(np.linspace(0, 1, self.L), device=self.device)    # splev's x, as plan()
+        self._status = torch.zeros((self.E, self.N), dtype=torch.int32, device=self.device)
+        io = self._plan_io = abi.AdrpRacePlanIO()
+        io.struct_size = ctypes.sizeof(abi.AdrpRacePlanIO)
+        io.num_envs, io.num_drones, io.ref_len = self.E, self.N, self.L
+        io.samples, io.ref, io.status = self._samples.data_ptr(), self._ref.data_ptr(), self._status.data_ptr()
+        io.phase = self._flags.data_ptr()      # torch.bool is one byte: [3][E * N]
+
+    def _replan_device(self, obs0, mask=None):
+        o = self._device_obs(obs0)
+        E, N = self.E, self.N
+        if not (o.dim() == 3 and tuple(o.shape[:2]) == (E, N) and o.shape[2] >= abi.PLAN_OBS_MIN and o.device == self.device
+                and o.stride(2) == 1 and (N == 1 or o.stride(0) == N * o.stride(1)) and o.stride(1 if N > 1 else 0) >= abi.PLAN_OBS_MIN):
+            raise ValueError(f"obs must be a float32 [{E}, {N}, D >= {abi.PLAN_OBS_MIN}] tensor on {self.device} with evenly "
+                             "strided rows")
+        io = self._plan_io
+        io.obs, io.obs_stride = o.data_ptr(), int(o.stride(1) if N > 1 else o.stride(0))
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
+            if mask.numel() != E:
+                raise ValueError(f"mask must have {E} elements")
+        io.mask = None if mask is None else mask.data_ptr()
+        lib = self._lib.load()
+        with torch.cuda.device(self.device):
+            self._status.zero_()
+            rc = lib.adrp_race_plan(ctypes.byref(io), self._lib._raw_stream(self.device.index))
+            if rc != 0:
+                raise self._lib.AdrpError(lib.adrp_last_error(None).decode())
+            bad = int((self._status & (abi.PLAN_NOT_IER0 | abi.PLAN_CEILING)).max())     # the one host read
+        if bad:
+            self._device_exceptions(o)
+
+    def _device_exceptions(self, o):
+        """the rare path: some drone's status has bit 0 (re-plan it on the host) or bit 1 (the ceiling)"""
+        st = self._status.cpu().numpy()
+        if (st & abi.PLAN_CEILING).any():
+            raise ValueError("Drone must stay below the ceiling")
+        for e, n in zip(*np.nonzero(st & abi.PLAN_NOT_IER0)):
+            row = o[e, n, :abi.PLAN_OBS_MIN].cpu().numpy()
+            self._ref[e, n] = torch.as_tensor(plan(row[0:2].astype(np.float64), row[12:28].astype(np.float64).reshape(4, 4)),
+                                              device=self.device)
+            self.host_fallbacks += 1
+
+    @property
+    def plan_status(self):
+        """planner="device": int32 [E, N] status words of the last replan (include/adrp.h adrp_race_plan)"""
+        return self._status
 
     @property
     def reference_trajectory(self):

@@ -19,8 +19,9 @@ record nothing, so the results do not depend on it.  All envs of a wave share on
 ``ep_time = k / ctrl_freq`` at step ``k`` (sim.py:79).
 
 Deviations from the reference, all deliberate: the runs are batched in waves, not sequential; the scripted
-controller still plans its spline on the host (scipy ``splprep``, one call per distinct start: ``E N`` calls per
-wave on the randomised levels); the other reference controllers (``HoverController``, the TwoGates scripted
+controller plans its spline on the host by default (scipy ``splprep``, one call per distinct observation row of
+the wave) and with ``planner="device"`` in one launch per wave (``adrp_race_plan``, the
+same FITPACK fit restated in csrc/spline_plan.h); the other reference controllers (``HoverController``, the TwoGates scripted
 one) are not built; there is no GUI timer.
 """
 import ctypes
@@ -61,7 +62,10 @@ class ControllerBank:
     RLControllerTwoGates) or ``None`` (the drone gets Command.NONE).  ``predict`` returns the encoded
     ``(codes int32 [E, N], args float64 [E, N, 14])`` pair ``env.step`` takes; the buffers are persistent."""
 
-    def __init__(self, env, controllers):
+    def __init__(self, env, controllers, planner="host"):
+        if planner not in ("host", "device"):
+            raise ValueError(f"planner must be 'host' or 'device', not {planner!r}")
+        self.planner = planner
         _need_gpu()
         self.lib = _lib.load()
         self.E, self.N, self.D = int(env.num_envs), int(env.NUM_DRONES), int(env.h.D)
@@ -109,7 +113,7 @@ class ControllerBank:
         if self.has_hardcoded:
             from .hardcoded import HardCodedCommander
             if self.commander is None:
-                self.commander = HardCodedCommander(obs0, delay=delay, device=self.device)
+                self.commander = HardCodedCommander(obs0, delay=delay, device=self.device, planner=self.planner)
                 self._io.ref_len = self.commander.L
                 self._io.ref = self.commander.reference_trajectory.data_ptr()
                 self._io.offset = self.commander._offset.data_ptr()
@@ -305,16 +309,20 @@ def _resolve(c, device):
 
 def simulate(config="level0", controller=("hardcoded",), n_runs=10, n_drones=2, gui=False, num_envs=None,
              racemode=RaceMode.COMPARE, precision="fp64", physics=Physics.PYB, seed=0, reward="env", obs_wrapper=0,
-             poll_every=16, max_steps=None, return_results=False, device=0):
+             poll_every=16, max_steps=None, return_results=False, device=0, planner="host"):
     """Evaluate the drones' controllers over ``n_runs`` races (scripts/sim.py::simulate): returns the list of
     episode times in run order, or the ``RaceResults`` with ``return_results=True``.
 
     ``controller``: one entry per drone or a single entry for all of them, each "hardcoded", a ``DevicePolicy``
     (mode "relative" / "absolute"), "zip:PATH" (an SB3 zip, loaded as a relative-mode policy) or None.
-    ``num_envs``: races per wave, ``min(n_runs, 4096)`` by default.  ``max_steps`` bounds one wave."""
+    ``num_envs``: races per wave, ``min(n_runs, 4096)`` by default.  ``max_steps`` bounds one wave.
+    ``planner``: where the "hardcoded" drones plan their splines at every wave's reset: "host" (scipy, one call
+    per distinct start) or "device" (one ``adrp_race_plan`` launch on the reset observation in place)."""
     from .envs.race import MultiRaceAviary
     if gui:
         raise ValueError("GUI / video recording are out of scope (DESIGN.md)")
+    if planner not in ("host", "device"):
+        raise ValueError(f"planner must be 'host' or 'device', not {planner!r}")
     n_runs, n_drones, poll_every = int(n_runs), int(n_drones), max(1, int(poll_every))
     if n_runs < 1:
         raise ValueError("n_runs must be at least 1")
@@ -332,7 +340,7 @@ def simulate(config="level0", controller=("hardcoded",), n_runs=10, n_drones=2, 
         if max_steps is None:
             # the longest episode has len * ctrl_freq + 2 steps (evaluation.evaluate_policy)
             max_steps = int(np.ceil(float(env.cfg.track.episode_len_sec) * env.CTRL_FREQ)) + 2
-        bank = ControllerBank(env, controllers)
+        bank = ControllerBank(env, controllers, planner=planner)
         res = RaceResults(E, n_drones, n_runs, env.device, env.CTRL_FREQ)
         with torch.cuda.device(env.device):
             for base in range(0, n_runs, E):

@@ -183,3 +183,16 @@ class AdrpRaceResultsIO(ctypes.Structure):
                 ("open", _p), ("run_return", _p), ("run_length", _p), ("gates", _p), ("finish", _p), ("elim", _p),
                 ("meta", _p), ("log_return", _p), ("log_length", _p), ("log_term", _p), ("log_trunc", _p),
                 ("log_gates", _p), ("log_finish", _p), ("log_elim", _p)]
+
+
+PLAN_KNOTS, PLAN_COEF, PLAN_OBS_MIN = 20, 16, 28       # ADRP_PLAN_*
+PLAN_NOT_IER0, PLAN_CEILING = 1, 2                     # adrp_race_plan status bits 0 / 1; n in bits 8..15, iterations 16..23
+
+
+class AdrpRacePlanIO(ctypes.Structure):
+    """adrp_race_plan_io (include/adrp.h): the caller-owned device buffers of the scripted racer's spline planner"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("ref_len", _i32),
+                ("obs_stride", _i32), ("reserved", _i32),
+                ("obs", _p), ("mask", _p), ("samples", _p), ("ref", _p), ("status", _p),
+                ("knots", _p), ("n_knots", _p), ("coef", _p), ("phase", _p)]

@@ -608,6 +608,51 @@ int adrp_race_results_step_env(const adrp_race_results_io* io, adrp_t* h, const 
                                const uint8_t* trunc, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Device spline planner of the scripted racer (user_controller/HardCodedController.py:63-115: 16 waypoints
+ * from the drone's start and the nominal gates, scipy splprep(s = 0.1), splev at L parameter values): what
+ * hardcoded.plan computes per drone on the host, for every (env, drone) of a wave in one launch.
+ * csrc/spline_plan.h (the fit, shared with the CPU program csrc/plan_host.cpp), csrc/plan_kernel.h.
+ * Handle-less like the race evaluation above: the caller owns every buffer, all on one device.
+ *
+ * One lane per (env, drone), slot e * N + n, reads the start x, y from obs[0:2] and the four gates' x, y from
+ * obs[12:28] of its observation row obs + slot * obs_stride (float32, widened to float64), fits in float64
+ * (FITPACK's fpparc: k = 3, unit weights, tol 1e-3, maxit 20) and the workgroup writes the samples
+ * ref[slot][j] = spline(samples[j]), j < L.  samples is the caller's table (np.linspace(0, 1, L)).  With a
+ * mask only the envs with mask[e] != 0 are planned; nothing of the other envs is read or written.
+ * status[slot]: bit 0 the fit did not end with FITPACK's ier = 0 (re-plan that drone on the host), bit 1 a
+ * sample z >= 2.5 (the reference's ceiling check), bits 8..15 the knot count n, bits 16..23 the iterations
+ * of the smoothing parameter.  Optional outputs: knots [E][N][20] (zero past n), n_knots [E][N], coef
+ * [E][N][3][16] (zero past n - 4); phase uint8 [3][E*N] (adrp_race_ctrl_io.phase) of the planned slots is cleared.
+ *
+ * Refused with ADRP_ERR_INVALID before any device call, through adrp_last_error(NULL): a NULL io, a
+ * struct_size mismatch, num_envs < 1, num_drones outside 1..ADRP_MAX_DRONES, ref_len < 2, obs_stride < 28,
+ * a NULL obs / samples / ref / status.
+ * --------------------------------------------------------------------------------------- */
+#define ADRP_PLAN_KNOTS 20          /* knots a 16-point cubic fit can have (m + k + 1) */
+#define ADRP_PLAN_COEF 16           /* coefficients per coordinate, at most */
+#define ADRP_PLAN_OBS_MIN 28        /* floats of an observation row the planner reads from */
+#define ADRP_PLAN_NOT_IER0 1        /* status bit 0 */
+#define ADRP_PLAN_CEILING 2         /* status bit 1 */
+typedef struct adrp_race_plan_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_plan_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  ref_len;         /* L >= 2 samples per trajectory */
+    int32_t  obs_stride;      /* floats between consecutive (env, drone) rows, >= 28 */
+    int32_t  reserved;
+    const float*   obs;       /* row e * N + n at obs + (e * N + n) * obs_stride */
+    const uint8_t* mask;      /* [E] or NULL: every env */
+    const double*  samples;   /* [L] */
+    double*  ref;             /* [E][N][L][3] out */
+    int32_t* status;          /* [E][N] out */
+    double*  knots;           /* [E][N][ADRP_PLAN_KNOTS] out, or NULL */
+    int32_t* n_knots;         /* [E][N] out, or NULL */
+    double*  coef;            /* [E][N][3][ADRP_PLAN_COEF] out, or NULL */
+    uint8_t* phase;           /* [3][E*N] cleared for the planned slots, or NULL */
+} adrp_race_plan_io;
+int adrp_race_plan(const adrp_race_plan_io* io, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Stand-alone batched DSLPIDControl (control/DSLPIDControl.py:9-259, control/BaseControl.py:21-95):
  * what examples/pid.py:126-147 and examples/downwash.py build one object per drone of, for users who
  * drive CtrlAviary themselves.  One controller handle holds `rows` independent controllers (one per

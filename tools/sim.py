@@ -5,7 +5,8 @@ python tools/sim.py --config level0 --controller hardcoded,zip:PATH --n_runs 409
 
 --controller: one entry per drone, comma-separated, or a single entry used for all drones: ``hardcoded``
 (HardCodedController), ``zip:PATH`` (an SB3 PPO zip driven as the RLController drives it; ``zip:PATH:absolute`` for
-the RLControllerTwoGates transform) or ``none``.  Prints the episode times (the reference's return value) and a
+the RLControllerTwoGates transform) or ``none``.  ``--planner device`` plans the hardcoded drones' splines on the GPU
+(one launch per wave) instead of with scipy on the host.  Prints the episode times (the reference's return value) and a
 per-drone table: finish rate, mean finish time, elimination rate, wins.
 """
 import argparse
@@ -37,11 +38,13 @@ def main(argv=None):
     ap.add_argument("--num_envs", type=int, default=None, help="races per wave (default min(n_runs, 4096))")
     ap.add_argument("--precision", default="fp64", choices=("fp32", "fp64"))
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--planner", default="host", choices=("host", "device"),
+                    help="where the hardcoded controllers plan their splines: scipy on the host, or one launch per wave")
     ap.add_argument("--quiet", action="store_true", help="do not print the episode times")
     args = ap.parse_args(argv)
     controllers = [None if c.lower() == "none" else c for c in args.controller.split(",")]
     res = simulate(args.config, controllers, n_runs=args.n_runs, n_drones=args.n_drones, num_envs=args.num_envs,
-                   precision=args.precision, seed=args.seed, return_results=True)
+                   precision=args.precision, seed=args.seed, return_results=True, planner=args.planner)
     if not args.quiet:
         print("episode times [s]:", " ".join(f"{t:.2f}" for t in res.episode_times))
     print(f"{args.n_runs} runs, mean episode time {res.episode_times.mean():.3f} s, "
