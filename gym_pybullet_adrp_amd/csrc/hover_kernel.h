@@ -36,9 +36,11 @@
 // Latency design (E = 4096 is 64 waves on 256 CUs: the kernel is one wave's critical
 // path): no divides or IEEE sqrt in the sub-step chain (reciprocal constants, 1-ulp
 // hardware rcp/sqrt/rsq), small-angle sin/cos polynomial, the lagged thrust axis is the
-// previous sub-step's z axis (carried, not recomputed), the action-ring loads
+// previous sub-step's z axis (carried, not recomputed), the state fields are addressed by one
+// 32-bit offset each on the scalar base (body_offsets) and loaded first, the action-ring loads
 // are issued at entry independent of the ring head, rows are written with 16-byte
-// per-lane stores straight from registers (no LDS, no barrier).
+// per-lane stores straight from registers (no LDS, no barrier) or, staged kernels, leave as one
+// coalesced block with the helper waves (HELP) taking the ring, the resets and the obs angles.
 #pragma once
 
 #include "adrp_device.h"
@@ -116,8 +118,9 @@ struct HoverReset {
 constexpr int kStepBlock = 64;   // envs per workgroup: one chain wave (E = 4096 -> 64 CUs)
 constexpr int kResetFields = 16; // pos 3, quat 4, vel 3, w 3, angv 3 of a reset state (HELP)
 // HELP kernels: two more helper waves beside the reset helper compute the obs row's pitch and yaw
-// from the chain's final quaternion while the chain computes the roll (ADRP_HOVER_ANGLE_HELPERS=0:
-// the chain computes all three, one helper wave)
+// from the chain's final quaternion, and the reset helper, idle by then, the roll; the chain meanwhile
+// rotates ω back to the world frame, converts the row and computes the reward
+// (ADRP_HOVER_ANGLE_HELPERS=0: the chain computes all three angles, one helper wave)
 #ifndef ADRP_PERSIST_SPLIT   // 0: a step of one env (launched or persistent) computes its three obs angles on one lane
 #define ADRP_PERSIST_SPLIT 1
 #endif
@@ -243,6 +246,16 @@ __device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn
     }
 }
 
+// true where the four prop heights are literal zeros (the compiled-in constants: cf2x_consts); device
+// constants, whatever their values, give false
+template <typename Real>
+__device__ __forceinline__ bool flat_props(const HoverConst<Real>& a) {
+    bool flat = true;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) flat = flat && __builtin_constant_p(a.pz[i]) && a.pz[i] == Real(0);
+    return flat;
+}
+
 // One Bullet stepSimulation of one drone after the reference's force calls, ω in the body frame
 // (st.wb; b.w is not touched: the caller rotates st.wb back once after the last sub-step).  On entry
 // st holds the thrust axis, the current z axis, R^T zs and |wb| of the pose b.q; on exit those of the
@@ -253,7 +266,7 @@ __device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn
 template <typename Real, int PH, bool EXT = false>
 __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
                                             const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
-                                            const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}) {
+                                            const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}, Real* vxy = nullptr) {
     constexpr bool GND = (PH == ADRP_PHYS_PYB_GND || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
@@ -261,9 +274,14 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     const V3<Real> zs = st.zs;
     V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
     const V3<Real> m3 = st.m3;
-    // P x m3 + tau_z m3
-    V3<Real> nb = v3(fmx(tau_z, m3.x, fmx(P.y, m3.z, -(P.z * m3.y))), fmx(tau_z, m3.y, fmx(P.z, m3.x, -(P.x * m3.z))),
-                     fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))));
+    // P x m3 + tau_z m3.  Flat props (literal pz = 0, the compiled-in drone): P.z is +0, and fma(P.y, m3.z,
+    // -(0 m3.y)) = P.y m3.z, fma(0, m3.x, c) = c but for the sign of an exact zero, so the two P.z products go
+    // (tests/test_hover_offchain_gpu.py holds the compiled kernel to the generic one, which keeps them)
+    V3<Real> nb = flat_props(a)
+                      ? v3(fmx(tau_z, m3.x, P.y * m3.z), fmx(tau_z, m3.y, -(P.x * m3.z)),
+                           fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))))
+                      : v3(fmx(tau_z, m3.x, fmx(P.y, m3.z, -(P.z * m3.y))), fmx(tau_z, m3.y, fmx(P.z, m3.x, -(P.x * m3.z))),
+                           fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))));
     if constexpr (GND) {
         // getLinkStates(computeForwardKinematics=1) refreshes the cached basis first (so the drag
         // below is applied in the current basis)
@@ -319,7 +337,14 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     clamp100_body(b.q, wb, ang, b.vel, K);
     st.wb = wb;
     st.wn = ang;
-    b.pos = v3(fmx(a.dt, b.vel.x, b.pos.x), fmx(a.dt, b.vel.y, b.pos.y), fmx(a.dt, b.vel.z, b.pos.z));
+    // (vxy: nothing in a sub-step reads pos.x / pos.y, so the caller may take this sub-step's horizontal
+    // velocity instead and run the same two sums itself afterwards, pyb_chain)
+    if (vxy) {
+        vxy[0] = b.vel.x; vxy[1] = b.vel.y;
+        b.pos.z = fmx(a.dt, b.vel.z, b.pos.z);
+    } else {
+        b.pos = v3(fmx(a.dt, b.vel.x, b.pos.x), fmx(a.dt, b.vel.y, b.pos.y), fmx(a.dt, b.vel.z, b.pos.z));
+    }
     // exp-map quaternion update (btMultiBody::stepPositionsMultiDof)
     if (ang > a.ang_max) ang = a.ang_max;          // |w| dt > ANGULAR_MOTION_THRESHOLD
     // sin(|w| dt / 2) / |w| = (dt / 2) sinc(|w| dt / 2): no reciprocal, and Bullet's small-angle
@@ -637,11 +662,122 @@ __device__ __forceinline__ void dslpid_rpm(const HoverConst<Real>& C, const Body
     }
 }
 
+// ---- state field addressing ----
+// The state is [field][E]: field k of env e lies k * E * sizeof(T) bytes behind the env's field 0.  Indexed
+// as f[k * E + e] every field costs three VALU instructions (add, sign extension, 64-bit shift-add) and
+// a 64-bit address pair that lives from the loads to the stores.  Here a lane walks the fields with ONE
+// 32-bit byte offset on the uniform base pointer, the saddr + voffset form of the global instructions: a
+// v_add_u32 of the stride per field, and the offsets (one VGPR each) serve the stores again.  (field_lane:
+// the offset is opaque to the optimiser, which would otherwise rebuild off0 + k * stride per field.)
+// The offsets are 32-bit, so the form holds while every field of the block, the PID fields included, ends
+// below 4 GiB: up to kFieldOffsetMaxBytes / ((HF_NBASE + HF_NPID) sizeof(T)) envs (field_offsets_fit;
+// adrp_internal.h states the bound).  Above it the accesses keep 64-bit indices: the hover step kernel
+// has both forms and the host picks one (W32); the other callers of load_body / store_body branch on E.
+constexpr uint64_t kFieldOffsetMaxBytes = uint64_t(1) << 32;
+template <typename T>
+__host__ __device__ constexpr uint32_t field_offsets_max_envs() {
+    return uint32_t(kFieldOffsetMaxBytes / (uint64_t(HF_NBASE + HF_NPID) * sizeof(T)));
+}
+template <typename T>
+__host__ __device__ constexpr bool field_offsets_fit(int E) {
+    return __builtin_expect(uint32_t(E) <= field_offsets_max_envs<T>(), 1);
+}
+__device__ __forceinline__ uint32_t field_lane(uint32_t off) {
+    asm("" : "+v"(off));
+    return off;
+}
+// keeps the value's uses behind (and its definition before) the side-effecting statements around it
+__device__ __forceinline__ void hold(double& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void hold(float& x) { asm volatile("" : "+v"(x)); }
+// Ends the 32-bit arm of a branch on field_offsets_fit.  Both arms finish with the same loads (or stores)
+// of the same fields; without a difference at their ends the optimiser sinks those into the join with the
+// address picked per field from the two forms (a 64-bit select each), which is worse than either.
+__device__ __forceinline__ void field_form_end() { asm volatile(""); }
+template <typename T>
+__device__ __forceinline__ T& field_at(T* base, uint32_t off) {
+    return *(T*)((const char*)base + off);   // (T may be const: the byte pointer drops it for the arithmetic only)
+}
+// the last use of an offset (the stores): the address is formed behind a statement that stays in the
+// store's own block, so it is not shared with the load's block as a 64-bit pair formed above both
+template <typename T>
+__device__ __forceinline__ T& field_last(T* base, uint32_t off) {
+    asm volatile("" : "+v"(off));
+    return *(T*)((const char*)base + off);
+}
+// byte offsets o[first .. first + n) of the lane's fields first .. first + n - 1 (off0: of its field 0)
+template <int N>
+__device__ __forceinline__ void field_run(uint32_t off0, uint32_t stride, int first, int n, uint32_t (&o)[N]) {
+    uint32_t off = first ? field_lane(off0 + uint32_t(first) * stride) : off0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+        o[first + i] = off;
+        if (i + 1 < n) off = field_lane(off + stride);
+    }
+}
+// the offsets of one env's Body fields (those the mode reads; the others stay unset and unused)
+template <typename Real>
+struct BodyOffs {
+    uint32_t o[HF_NBASE];
+};
+template <typename Real>
+__device__ __forceinline__ BodyOffs<Real> body_offsets(int E, int e, bool lag, bool drag, bool dyn) {
+    BodyOffs<Real> r;
+    const uint32_t stride = uint32_t(E) * uint32_t(sizeof(Real)), off0 = uint32_t(e) * uint32_t(sizeof(Real));
+    field_run(off0, stride, HF_POS, HF_LAST_RPM - HF_POS, r.o);   // pos, quat, vel, omega
+    if (drag) field_run(off0, stride, HF_LAST_RPM, 4, r.o);
+    if (dyn) field_run(off0, stride, HF_ANGV, 3, r.o);
+    if (lag) field_run(off0, stride, HF_LINK_QUAT, 4, r.o);
+    return r;
+}
+
+template <typename Real>
+__device__ __forceinline__ void load_body_at(const Real* f, const BodyOffs<Real>& k, Body<Real>& b, bool lag,
+                                             bool drag, bool dyn) {
+    b.pos = v3(field_at(f, k.o[HF_POS + 0]), field_at(f, k.o[HF_POS + 1]), field_at(f, k.o[HF_POS + 2]));
+    b.q = {field_at(f, k.o[HF_QUAT + 0]), field_at(f, k.o[HF_QUAT + 1]), field_at(f, k.o[HF_QUAT + 2]),
+           field_at(f, k.o[HF_QUAT + 3])};
+    b.vel = v3(field_at(f, k.o[HF_VEL + 0]), field_at(f, k.o[HF_VEL + 1]), field_at(f, k.o[HF_VEL + 2]));
+    b.w = v3(field_at(f, k.o[HF_OMEGA + 0]), field_at(f, k.o[HF_OMEGA + 1]), field_at(f, k.o[HF_OMEGA + 2]));
+    if (lag) b.ql = {field_at(f, k.o[HF_LINK_QUAT + 0]), field_at(f, k.o[HF_LINK_QUAT + 1]),
+                     field_at(f, k.o[HF_LINK_QUAT + 2]), field_at(f, k.o[HF_LINK_QUAT + 3])};
+    else b.ql = b.q;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = drag ? field_at(f, k.o[HF_LAST_RPM + i]) : Real(0);
+    if (dyn) b.angv = v3(field_at(f, k.o[HF_ANGV + 0]), field_at(f, k.o[HF_ANGV + 1]), field_at(f, k.o[HF_ANGV + 2]));
+    else b.angv = v3(Real(0), Real(0), Real(0));
+}
+template <typename Real>
+__device__ __forceinline__ void store_body_at(Real* f, const BodyOffs<Real>& k, const Body<Real>& b, bool lag,
+                                              bool drag, bool dyn) {
+    field_last(f, k.o[HF_POS + 0]) = b.pos.x; field_last(f, k.o[HF_POS + 1]) = b.pos.y; field_last(f, k.o[HF_POS + 2]) = b.pos.z;
+    field_last(f, k.o[HF_QUAT + 0]) = b.q.x; field_last(f, k.o[HF_QUAT + 1]) = b.q.y;
+    field_last(f, k.o[HF_QUAT + 2]) = b.q.z; field_last(f, k.o[HF_QUAT + 3]) = b.q.w;
+    field_last(f, k.o[HF_VEL + 0]) = b.vel.x; field_last(f, k.o[HF_VEL + 1]) = b.vel.y; field_last(f, k.o[HF_VEL + 2]) = b.vel.z;
+    field_last(f, k.o[HF_OMEGA + 0]) = b.w.x; field_last(f, k.o[HF_OMEGA + 1]) = b.w.y; field_last(f, k.o[HF_OMEGA + 2]) = b.w.z;
+    if (lag) {
+        field_last(f, k.o[HF_LINK_QUAT + 0]) = b.ql.x; field_last(f, k.o[HF_LINK_QUAT + 1]) = b.ql.y;
+        field_last(f, k.o[HF_LINK_QUAT + 2]) = b.ql.z; field_last(f, k.o[HF_LINK_QUAT + 3]) = b.ql.w;
+    }
+    if (drag) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) field_last(f, k.o[HF_LAST_RPM + i]) = b.prev_rpm[i];
+    }
+    if (dyn) {
+        field_last(f, k.o[HF_ANGV + 0]) = b.angv.x; field_last(f, k.o[HF_ANGV + 1]) = b.angv.y;
+        field_last(f, k.o[HF_ANGV + 2]) = b.angv.z;
+    }
+}
+
 template <typename Real>
 __device__ __forceinline__ void load_body(const HoverArgs<Real>& a, int e, Body<Real>& b, bool lag, bool drag,
                                           bool dyn) {
     const int E = a.E;
     const Real* f = a.f;
+    if (field_offsets_fit<Real>(E)) {
+        load_body_at(f, body_offsets<Real>(E, e, lag, drag, dyn), b, lag, drag, dyn);
+        field_form_end();
+        return;
+    }
     b.pos = v3(f[(HF_POS + 0) * E + e], f[(HF_POS + 1) * E + e], f[(HF_POS + 2) * E + e]);
     b.q = {f[(HF_QUAT + 0) * E + e], f[(HF_QUAT + 1) * E + e], f[(HF_QUAT + 2) * E + e], f[(HF_QUAT + 3) * E + e]};
     b.vel = v3(f[(HF_VEL + 0) * E + e], f[(HF_VEL + 1) * E + e], f[(HF_VEL + 2) * E + e]);
@@ -660,6 +796,11 @@ __device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, cons
                                            bool drag, bool dyn) {
     const int E = a.E;
     Real* f = a.f;
+    if (field_offsets_fit<Real>(E)) {
+        store_body_at(f, body_offsets<Real>(E, e, lag, drag, dyn), b, lag, drag, dyn);
+        field_form_end();
+        return;
+    }
     f[(HF_POS + 0) * E + e] = b.pos.x; f[(HF_POS + 1) * E + e] = b.pos.y; f[(HF_POS + 2) * E + e] = b.pos.z;
     f[(HF_QUAT + 0) * E + e] = b.q.x; f[(HF_QUAT + 1) * E + e] = b.q.y;
     f[(HF_QUAT + 2) * E + e] = b.q.z; f[(HF_QUAT + 3) * E + e] = b.q.w;
@@ -686,7 +827,7 @@ __device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, cons
 struct NoExtForce {};
 template <typename Real, int PH, int SC, bool DRAG, typename Ext>
 __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>& b, const Real rpm_in[4], bool lag,
-                                          Ext ext) {
+                                          Ext ext, V3<Real>* wb_out = nullptr, Real* vxy = nullptr) {
     constexpr bool EXT = !__is_same(Ext, NoExtForce);
     // (a local copy: nothing the sub-steps store can alias it, so what depends on the RPMs alone is
     // computed once for the unrolled sub-steps)
@@ -698,7 +839,11 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
         const Real r2 = rpm[i] * rpm[i];
         const Real f = r2 * C.kf;
         sum_f += f;
-        P = P + v3(f * C.px[i], f * C.py[i], f * C.pz[i]);
+        // the reference drone's props sit in the body plane: a literal pz = 0 adds f * 0 = +0 (f >= 0) to
+        // +0, so P.z stays +0 without the multiply-adds (race_pyb_substep_r's idiom; flat_props below)
+        const bool pz0 = __builtin_constant_p(C.pz[i]) && C.pz[i] == Real(0);
+        const Real fx = f * C.px[i], fy = f * C.py[i], fz = f * C.pz[i];   // (products and sums in separate
+        P = v3(P.x + fx, P.y + fy, pz0 ? P.z : P.z + fz);                  //  statements: no contraction, as before)
         t2 += (i & 1) ? -r2 : r2;
     }
     const Real tau_z = t2 * C.km;    // KM*(rpm0^2 - rpm1^2 + rpm2^2 - rpm3^2), IROS sign
@@ -729,19 +874,25 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
     st.wn = hsqrt_nn_(dot(b.w, b.w), K);
     st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
     bool touched = false;
-    auto substep = [&]() {
+    // vxy (SC > 0, no external force): the horizontal position is left at its value before the chain and the
+    // SC sub-steps' horizontal velocities come back in vxy[2 s], vxy[2 s + 1]: the caller runs
+    // pos.x = fma(dt, vxy[2 s], pos.x), likewise y, in order (pos_xy_sums: the same operations, the same bits)
+    auto substep = [&](int s) {
         if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
-        else touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K);
+        else touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K, V3<Real>{}, vxy ? vxy + 2 * s : nullptr);
 #pragma unroll
         for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
     };
     if constexpr (SC > 0) {
 #pragma unroll
-        for (int s = 0; s < SC; ++s) substep();
+        for (int s = 0; s < SC; ++s) substep(s);
     } else {
-        for (int s = 0; s < C.S; ++s) substep();
+        for (int s = 0; s < C.S; ++s) substep(s);
     }
-    b.w = mul(rot_fm(b.q), st.wb);   // state, obs and the stored link_quat stay in the world frame
+    // state, obs and the stored link_quat stay in the world frame (wb_out: the caller rotates back itself,
+    // b.w = rot_fm(b.q) wb, where it has a wait to fill)
+    if (wb_out) *wb_out = st.wb;
+    else b.w = mul(rot_fm(b.q), st.wb);
     return touched;
 }
 
@@ -776,7 +927,10 @@ __device__ __forceinline__ void stage_row(float4* lds_row, const float o12[12], 
 // SYS: the action rows live in host-mapped memory written by the host while the kernel runs
 // (hover_persist.h): 1 = they are read with system-scope loads, which no GPU cache serves; 2 = the
 // caller already read them (pre[0..A-1], the persistent kernel's line mode).
-template <typename Real, int PH, int A, int B, int SC, bool STG = false, int CTL = 0, bool HELP = false, int SYS = 0>
+// FO: the state's field addressing (body_offsets): 1 = 32-bit offsets (the host saw that E fits), 0 = 64-bit
+// indices, 2 = decided here from E (a branch at the loads and at the stores).
+template <typename Real, int PH, int A, int B, int SC, bool STG = false, int CTL = 0, bool HELP = false, int SYS = 0,
+          int FO = 2>
 __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const HoverConst<Real>& C,
                                                 const float* pre = nullptr) {
     constexpr int BR = B > 0 ? B : 1;
@@ -786,11 +940,12 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     __shared__ Real rs_body[HELP ? kResetFields * kStepBlock : 1];
     __shared__ float rs_obs[HELP ? 12 * kStepBlock : 1];
     __shared__ float4 rows[STG ? kStepBlock * kRowF4 : 1];
-    // ANG: the obs row's pitch / yaw are computed by two more helper waves from the chain's final
-    // quaternion (LDS) while the chain computes the roll: the chain's tail holds one of the three
-    // float64 atan2-class evaluations instead of three
+    // ANG: the obs row's angles are computed by the helper waves from the chain's final quaternion (LDS):
+    // pitch and yaw by two more waves, the roll by the reset helper, whose own work ends before barrier A.
+    // The chain's tail holds none of the three float64 atan2-class evaluations
     constexpr bool ANG = HELP && angle_helpers<Real>();
     __shared__ Real ang_q[ANG ? 4 * kStepBlock : 1];
+    __shared__ Real ang_r[ANG ? kStepBlock : 1];
     __shared__ Real ang_p[ANG ? kStepBlock : 1];
     __shared__ float ang_y[ANG ? kStepBlock : 1];
     // the block's coalesced copy-out dealt over its waves: float4 columns [cb(w), cb(w + 1)) of the
@@ -862,7 +1017,11 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             }
             reinterpret_cast<float4*>(a.ring)[size_t(head) * E + he] = av;
             __syncthreads();   // A: reset states and ring rows in LDS
-            if constexpr (ANG) __syncthreads();   // C
+            if constexpr (ANG) {   // this wave is idle from here to the copy-out: it takes the roll
+                const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
+                ang_r[tl] = euler_roll_u(q);
+                __syncthreads();   // C
+            }
             __syncthreads();   // B: the chain wave's kinematic parts and reset rows
             // this wave's part of the block's coalesced copy-out
             float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
@@ -880,7 +1039,25 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     const int D = B > 0 ? 12 + B * A : a.D;
     if (e >= E) return;
     RACE_MARK(t0);
-    // ---- issue every load up front: action, the whole ring, ints, state ----
+    // ---- issue every load up front: state (the chain's first operands) and ints, action, the whole ring ----
+    // one 32-bit byte offset per field on the uniform base (body_offsets), kept for the stores
+    const bool fit = FO == 2 ? field_offsets_fit<Real>(E) : FO == 1;
+    const bool lag = C.link_lag && !DYN;
+    // (the offsets are formed on both sides of the branch, so that they are no merged values at the stores)
+    const BodyOffs<Real> fo = body_offsets<Real>(E, e, lag, DRAG, DYN);
+    uint32_t io[HI_N];
+    field_run(uint32_t(e) * 4u, uint32_t(E) * 4u, 0, HI_N, io);
+    Body<Real> b;
+    int32_t sc, ep, head_ld;
+    if (fit) {
+        load_body_at<Real>(a.f, fo, b, lag, DRAG, DYN);
+        sc = field_at(a.ist, io[HI_STEP]); ep = field_at(a.ist, io[HI_EPISODE]); head_ld = field_at(a.ist, io[HI_RING_HEAD]);
+        field_form_end();
+    } else {
+        load_body(a, e, b, lag, DRAG, DYN);
+        sc = a.ist[HI_STEP * E + e]; ep = a.ist[HI_EPISODE * E + e]; head_ld = a.ist[HI_RING_HEAD * E + e];
+    }
+    const int32_t head = head_ld;
     float act[A];
     if constexpr (SYS == 2) {
 #pragma unroll
@@ -908,28 +1085,41 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             for (int j = 0; j < A; ++j) ring[p][j] = a.ring[(size_t(p) * E + e) * A + j];
         }
     }
-    int32_t sc = a.ist[HI_STEP * E + e], ep = a.ist[HI_EPISODE * E + e];
-    const int32_t head = a.ist[HI_RING_HEAD * E + e];
-    const bool lag = C.link_lag && !DYN;
-    Body<Real> b;
-    load_body(a, e, b, lag, DRAG, DYN);
     // ---- _preprocessAction: RPM = HOVER_RPM * (1 + 0.05 a), the gain in float32 (NEP 50),
     //      or the DSLPIDControl output for the PID action types ----
     Real rpm[4];
     if constexpr (CTL != 0) {
         static_assert(A == (CTL == ADRP_ACT_PID ? 3 : CTL == ADRP_ACT_VEL ? 4 : 1), "PID action width");
         Real ctl[HF_NPID];
+        uint32_t po[HF_PID + HF_NPID];
+        field_run(uint32_t(e) * uint32_t(sizeof(Real)), uint32_t(E) * uint32_t(sizeof(Real)), HF_PID, HF_NPID, po);
+        if (fit) {
 #pragma unroll
-        for (int k = 0; k < HF_NPID; ++k) ctl[k] = a.f[(HF_PID + k) * E + e];
+            for (int k = 0; k < HF_NPID; ++k) ctl[k] = field_at(a.f, po[HF_PID + k]);
+            field_form_end();
+        } else {
+#pragma unroll
+            for (int k = 0; k < HF_NPID; ++k) ctl[k] = a.f[(HF_PID + k) * E + e];
+        }
         dslpid_rpm<Real, CTL>(C, b, act, ctl, rpm);
+        if (fit) {
 #pragma unroll
-        for (int k = 0; k < HF_NPID; ++k) a.f[(HF_PID + k) * E + e] = ctl[k];
+            for (int k = 0; k < HF_NPID; ++k) field_last(a.f, po[HF_PID + k]) = ctl[k];
+            field_form_end();
+        } else {
+#pragma unroll
+            for (int k = 0; k < HF_NPID; ++k) a.f[(HF_PID + k) * E + e] = ctl[k];
+        }
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) rpm[i] = C.hover_rpm * Real(rpm_gain(act[A == 1 ? 0 : i]));
     }
     // ---- sub-step loop (BaseAviary.py:347-376) ----
     bool touched = false;
+    V3<Real> wbf = v3(Real(0), Real(0), Real(0));   // ANG: the chain's final ω, still in the body frame
+    // ANG with unrolled sub-steps: pos.x / pos.y are summed behind barrier A too (pyb_chain's vxy)
+    constexpr bool LATE_XY = ANG && !DYN && SC > 0;
+    Real vxy[LATE_XY ? 2 * SC : 2] = {};
 #ifdef ADRP_RACE_TIMING
     // loads landed: the rpm gains and the state are consumed by the first sub-step
     __builtin_amdgcn_s_waitcnt(0);
@@ -943,7 +1133,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
         }
     } else {
-        touched = pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{});
+        touched = pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{}, ANG ? &wbf : nullptr, LATE_XY ? vxy : nullptr);
     }
     RACE_MARK(t2);
     if (touched && a.contact_count && (!split || threadIdx.x == 0)) atomicAdd(a.contact_count, 1);
@@ -957,6 +1147,21 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         for (int j = 0; j < A; ++j) a.ring[(size_t(head) * E + e) * A + j] = act[j];
     const int BB = B > 0 ? B : a.B;                    // ring length (runtime for the generic kernel)
     const int head1 = head + 1 == BB ? 0 : head + 1;
+    // the state and the ints leave through the offsets of the loads
+    auto store_state = [&]() {
+        if (fit) {
+            store_body_at<Real>(a.f, fo, b, lag, DRAG, DYN);
+            field_last(a.ist, io[HI_STEP]) = sc;
+            field_last(a.ist, io[HI_EPISODE]) = ep;
+            field_last(a.ist, io[HI_RING_HEAD]) = head1;
+            field_form_end();
+        } else {
+            store_body(a, e, b, lag, DRAG, DYN);
+            a.ist[HI_STEP * E + e] = sc;
+            a.ist[HI_EPISODE * E + e] = ep;
+            a.ist[HI_RING_HEAD * E + e] = head1;
+        }
+    };
     // ---- obs / reward / terminated / truncated (HoverAviary.py:68-117) ----
     float o12[12];
     V3<Real> rpy;
@@ -965,9 +1170,27 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         ang_q[tl] = b.q.x; ang_q[kStepBlock + tl] = b.q.y; ang_q[2 * kStepBlock + tl] = b.q.z;
         ang_q[3 * kStepBlock + tl] = b.q.w;
         __syncthreads();   // A: the quaternion out; the reset helper's states and ring rows in
-        rpy.x = euler_roll_u(b.q);
-        const V3<Real> w = C.physics == ADRP_PHYS_DYN ? b.angv : b.w;   // hover_obs12's row, pitch / yaw below
-        o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z); o12[3] = float(rpy.x);
+        // while the three helper waves take one angle each, the chain does what only it can: ω back to the
+        // world frame (deferred by pyb_chain), the conversions, the reward and the angle-free truncation tests
+        // (hold: arithmetic carries no order against a barrier, and the compiler had placed most of this
+        // before A and the rest after C, leaving the chain to wait at C with nothing to do; what the work
+        // starts from is taken behind A here, and what it gives is finished before C below)
+        hold(b.q.x); hold(b.q.y); hold(b.q.z); hold(b.q.w);
+        hold(wbf.x); hold(wbf.y); hold(wbf.z);
+        hold(b.pos.x); hold(b.pos.y); hold(b.pos.z);
+        if constexpr (LATE_XY) {   // the horizontal position sums of the sub-steps, deferred to here
+#pragma unroll
+            for (int k = 0; k < 2 * SC; ++k) hold(vxy[k]);
+#pragma unroll
+            for (int s = 0; s < SC; ++s) {
+                b.pos.x = fmx(C.dt, vxy[2 * s], b.pos.x);
+                b.pos.y = fmx(C.dt, vxy[2 * s + 1], b.pos.y);
+            }
+        }
+        hold(b.vel.x); hold(b.vel.y); hold(b.vel.z);
+        if constexpr (!DYN) b.w = mul(rot_fm(b.q), wbf);
+        const V3<Real> w = C.physics == ADRP_PHYS_DYN ? b.angv : b.w;   // hover_obs12's row, the angles below
+        o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z);
         o12[6] = float(b.vel.x); o12[7] = float(b.vel.y); o12[8] = float(b.vel.z);
         o12[9] = float(w.x);     o12[10] = float(w.y);    o12[11] = float(w.z);
     } else if (split) {
@@ -980,15 +1203,20 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     const Real r = Real(2) - d2 * d2;
     a.rew[e] = float(r > Real(0) ? r : Real(0));
     const bool te = d2 < Real(1e-8);   // |target - pos| < 1e-4
-    bool tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) ||
-              fabs_(rpy.x) > Real(0.4) || sc >= C.trunc_steps;
+    bool tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) || sc >= C.trunc_steps;
     if constexpr (ANG) {
-        __syncthreads();   // C: the helpers' pitch and yaw
+        hold(b.w.x); hold(b.w.y); hold(b.w.z);
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (k < 3 || k > 5) hold(o12[k]);
+        __syncthreads();   // C: the helpers' roll, pitch and yaw
+        rpy.x = ang_r[threadIdx.x];
         rpy.y = ang_p[threadIdx.x];
+        o12[3] = float(rpy.x);
         o12[4] = float(rpy.y);
         o12[5] = ang_y[threadIdx.x];
     }
-    tr = tr || fabs_(rpy.y) > Real(0.4);
+    tr = tr || fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
     a.term[e] = te;
     a.trunc[e] = tr;
     sc += C.S;
@@ -1067,10 +1295,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         RACE_SET(t4);
         // the state leaves first: its registers are free before the copy-out (holding both
         // spilled the copy-out buffer to scratch)
-        store_body(a, e, b, lag, DRAG, DYN);
-        a.ist[HI_STEP * E + e] = sc;
-        a.ist[HI_EPISODE * E + e] = ep;
-        a.ist[HI_RING_HEAD * E + e] = head1;
+        store_state();
         __syncthreads();
         float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
         constexpr int KC = cb(1);   // HELP: the helper waves copy the other columns
@@ -1098,10 +1323,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     }
     RACE_MARK(t5);
     if constexpr (!STG) {
-        store_body(a, e, b, lag, DRAG, DYN);
-        a.ist[HI_STEP * E + e] = sc;
-        a.ist[HI_EPISODE * E + e] = ep;
-        a.ist[HI_RING_HEAD * E + e] = head1;
+        store_state();
     }
 #ifdef ADRP_RACE_TIMING
     RACE_MARK(t6);
@@ -1132,7 +1354,8 @@ struct HoverTail {
 // DEF: compiled-in cf2x_consts (the reference default) instead of the device block.
 // STG: LDS-staged coalesced obs rows (host: only when E % kStepBlock == 0).
 // Launch with kStepBlock threads per workgroup.
-template <typename Real, int PH, int A, int B, bool DEF, bool STG = false, int CTL = 0, bool HELP = false>
+// W32: the state fields are addressed by 32-bit byte offsets (host: only while field_offsets_fit(E)).
+template <typename Real, int PH, int A, int B, bool DEF, bool STG = false, int CTL = 0, bool HELP = false, bool W32 = true>
 __global__ void __launch_bounds__(256) hover_step_kernel(Real* f, float* ring, int32_t* ist, const float* act,
                                                          float* obs, float* rew, int E, HoverTail<Real> t) {
     HoverArgs<Real> a;
@@ -1143,9 +1366,9 @@ __global__ void __launch_bounds__(256) hover_step_kernel(Real* f, float* ring, i
     a.E = E; a.B = t.B; a.D = t.D; a.autoreset = t.autoreset;
     if constexpr (DEF) {
         constexpr HoverConst<Real> C = cf2x_consts<Real>(PH);
-        hover_step_body<Real, PH, A, B, C.S, STG, CTL, HELP>(a, C);
+        hover_step_body<Real, PH, A, B, C.S, STG, CTL, HELP, 0, W32 ? 1 : 0>(a, C);
     } else {
-        hover_step_body<Real, PH, A, B, 0, STG, CTL, HELP>(a, *a.c);
+        hover_step_body<Real, PH, A, B, 0, STG, CTL, HELP, 0, W32 ? 1 : 0>(a, *a.c);
     }
 }
 

@@ -17,17 +17,25 @@ static void launch(K kernel, dim3 grid, dim3 blk, hipStream_t s, const HoverArgs
     launch_profiled(h, kernel, grid, blk, s, a.f, a.ring, a.ist, a.act, a.obs, a.rew, a.E, t);
 }
 
-template <typename Real, int A, int B, bool DEF, bool STG = false, int CTL = 0, bool HELP = false>
-static void launch_step_ph(const HoverArgs<Real>& a, int physics, dim3 grid, hipStream_t s, adrp_t* h) {
+template <typename Real, int A, int B, bool DEF, bool STG, int CTL, bool HELP, bool W32>
+static void launch_step_w(const HoverArgs<Real>& a, int physics, dim3 grid, hipStream_t s, adrp_t* h) {
     const dim3 blk(HELP ? (1 + help_waves<Real>()) * kBlock : kBlock);   // HELP: + the reset helper (and angle helper) waves
     switch (physics) {
-        case ADRP_PHYS_PYB: launch(hover_step_kernel<Real, ADRP_PHYS_PYB, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
-        case ADRP_PHYS_DYN: launch(hover_step_kernel<Real, ADRP_PHYS_DYN, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
-        case ADRP_PHYS_PYB_GND: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_GND, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
-        case ADRP_PHYS_PYB_DRAG: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_DRAG, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
-        case ADRP_PHYS_PYB_DW: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_DW, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
-        default: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_GND_DRAG_DW, A, B, DEF, STG, CTL, HELP>, grid, blk, s, a, h); break;
+        case ADRP_PHYS_PYB: launch(hover_step_kernel<Real, ADRP_PHYS_PYB, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
+        case ADRP_PHYS_DYN: launch(hover_step_kernel<Real, ADRP_PHYS_DYN, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
+        case ADRP_PHYS_PYB_GND: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_GND, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
+        case ADRP_PHYS_PYB_DRAG: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_DRAG, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
+        case ADRP_PHYS_PYB_DW: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_DW, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
+        default: launch(hover_step_kernel<Real, ADRP_PHYS_PYB_GND_DRAG_DW, A, B, DEF, STG, CTL, HELP, W32>, grid, blk, s, a, h); break;
     }
+}
+
+// the state fields by 32-bit byte offsets while the block fits them (kHoverOffsetMaxEnvs), by 64-bit
+// indices above: the same kernel otherwise
+template <typename Real, int A, int B, bool DEF, bool STG = false, int CTL = 0, bool HELP = false>
+static void launch_step_ph(const HoverArgs<Real>& a, int physics, dim3 grid, hipStream_t s, adrp_t* h) {
+    if (uint32_t(a.E) <= kHoverOffsetMaxEnvs<Real>) launch_step_w<Real, A, B, DEF, STG, CTL, HELP, true>(a, physics, grid, s, h);
+    else launch_step_w<Real, A, B, DEF, STG, CTL, HELP, false>(a, physics, grid, s, h);
 }
 
 template <typename Real>
