@@ -762,11 +762,7 @@ __device__ __forceinline__ void mellinger_fw(RDrone<Real>& d, const float sp[3],
     const float itn = FAST ? __builtin_amdgcn_rcpf(tn) : 0.0f;
     // !FAST: the C float divisions, correctly rounded through one float64 reciprocal per divisor
     // (f64::fdiv_rcp: the same bits as x / y, a third of the instructions for three quotients)
-#ifdef ADRP_EXP_FDIV_IEEE   // measurement-only: the plain IEEE float divisions (A/B of fdiv_rcp)
-#define FDIV_(x, ry, y) ((x) / (y))
-#else
-#define FDIV_(x, ry, y) f64::fdiv_rcp((x), (ry))
-#endif
+#define FDIV_(x, ry, y) f64::fdiv_rcp((x), (ry))   // (y: the divisor itself, for reading)
     const double rtn = FAST ? 0.0 : f64::rcp(double(tn));
     const float zd0 = FAST ? tx * itn : FDIV_(tx, rtn, tn), zd1 = FAST ? ty * itn : FDIV_(ty, rtn, tn),
                 zd2 = FAST ? tz * itn : FDIV_(tz, rtn, tn);
@@ -1917,7 +1913,9 @@ __global__ void __launch_bounds__(kRaceBlock * (PRE ? 1 + kRaceHelpers : 1)) rac
         // the 7 rays span the rectangle {g + t u + z e_z : |t| <= 0.15, |z - h| <= half};
         // drones whose bounding sphere (about pos: |z offset| + cylinder radius) misses it
         // cannot be hit, and a pass needs this lane's own drone to be hit
-        const Real br = fabs_(C.coll_zoff) + hsqrt_(C.coll_r * C.coll_r + C.coll_hh * C.coll_hh) +
+        // (the slack is 1e-10 in fp64 here and 1e-5 in race_step_q4: history, not design; the mask
+        // is a conservative pre-filter, so the decision is the same either way)
+        const Real br =fabs_(C.coll_zoff) + hsqrt_(C.coll_r * C.coll_r + C.coll_hh * C.coll_hh) +
                         (sizeof(Real) == 4 ? Real(1e-5) : Real(1e-10));
         uint32_t near = 0;
 #pragma unroll

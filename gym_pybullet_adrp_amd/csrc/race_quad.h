@@ -120,14 +120,6 @@ __device__ __forceinline__ Real euler_axis_q4(Q4<Real> q, int a) {
 // arithmetic as mellinger_compute<Real> (FP contraction off; fp32: reciprocal multiplies, fp64:
 // numpy's correctly rounded divisions (by constants: divc_) and the firmware's C float divisions),
 // split across the quad.
-// measurement-only (make devx XD=-DADRP_EXP_DUP_...): a phase evaluated twice, the second pass
-// made to wait for the first through an empty asm, so the kernel's time grows by the phase's cost on
-// the chain while every result (and so the trajectory) is unchanged
-template <typename T, typename U>
-__device__ __forceinline__ void exp_dep(T& x, const U& after) { asm volatile("" : "+v"(x) : "v"(after)); }
-template <typename T>
-__device__ __forceinline__ void exp_sink(const T& x) { asm volatile("" ::"v"(x)); }
-
 template <typename T>
 __device__ __forceinline__ T sel3(const T (&v)[3], int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }
 
@@ -192,18 +184,7 @@ __device__ __forceinline__ void mellinger_q4(RDrone<Real>& d, const Lpf& lpf, co
             // (a quad split of the firmware, one division per lane for the thrust / z_des / y_des
             // components and DPP broadcasts, measured slower in both precisions: +1.1 us fp64,
             // +0.1 us fp32 on config 4, A/B round 4)
-#ifdef ADRP_EXP_DUP_FW
-            {
-                RDrone<Real> d2 = d;
-                mellinger_fw<Real, F32, false>(d2, sp, xc_x, xc_y, gyro, pos, vel, Rm);
-                float p0 = pos[0];
-                exp_dep(p0, d2.ctl[0]);
-                const float pos2[3] = {p0, pos[1], pos[2]};
-                mellinger_fw<Real, F32, false>(d, sp, xc_x, xc_y, gyro, pos2, vel, Rm);
-            }
-#else
             mellinger_fw<Real, F32, false>(d, sp, xc_x, xc_y, gyro, pos, vel, Rm);
-#endif
         }
         CP_MARK(m2);
         CP_ADD(2, m2 - m1);
@@ -568,11 +549,7 @@ __device__ __forceinline__ void race_reset_q4(const RaceArgs<Real>& a, const Rac
     RESET_MARK(3);
     uint32_t gin, oin, amb, camb_all;
     bool ccert;
-#ifdef ADRP_EXP_RESET_NOQ
-    gin = oin = amb = camb_all = 0; ccert = false;
-#else
     track_bounds_q4(C, own, ds, Real(0.45), Real(0), ql, false, gin, oin, amb, camb_all, ccert);
-#endif
     uint32_t mine = amb & ((0x1fu << (kGateParts * ql)) | (0x3u << (kObstBit0 + kObstParts * ql)));
     uint32_t g2 = 0, o2 = 0;
     while (mine) {   // this lane's undecided parts (track_query)
@@ -588,11 +565,7 @@ __device__ __forceinline__ void race_reset_q4(const RaceArgs<Real>& a, const Rac
     RESET_MARK(4);
     Real row0[15];
     const V3<Real> zero = v3(Real(0), Real(0), Real(0));
-#ifdef ADRP_EXP_RESET_NOROW
-    for (int k = 0; k < 15; ++k) row0[k] = T.v[k];
-#else
     race_obs_row_rpy(C, T, npos, nominal_rpy(C, dn), zero, zero, 0, obs_row, owner, row0, gin, oin);
-#endif
     RESET_MARK(5);
     // the nominal Euler angles (RaceConst::nom_rpy, race_const_init_kernel)
     const V3<Real> nrpy = nominal_rpy(C, dn);
@@ -950,14 +923,6 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
     if constexpr (DRAWS) {   // sub-steps s = ql, ql + 4, ... of this drone
         quad_draws<Real>(H, pre_draws, a.seed, gid, ep, dn, sc0, ql, qd, H.S);
         __syncthreads();
-#ifdef ADRP_EXP_DUP_DRAWS
-        {
-            uint32_t ep2 = ep;
-            exp_dep(ep2, pre_draws[tl]);
-            quad_draws<Real>(H, pre_draws, a.seed, gid, ep2, dn, sc0, ql, qd, H.S);
-            __syncthreads();
-        }
-#endif
     }
     // lane-distributed controller state: axis cax of the rate history and the gyro filter
     Real prv = sel3(d.prev_rpy, cax);
@@ -988,15 +953,7 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
         } else {
             V3<Real> Fx = v3(Real(0), Real(0), Real(0)), Tx = v3(Real(0), Real(0), Real(0));
             if constexpr (PH == ADRP_PHYS_PYB_DW || PH == ADRP_PHYS_PYB_GND_DRAG_DW) {
-#ifdef ADRP_EXP_DUP_DW
-              V3<Real> dwp = d.pos;
-              for (int rep = 0; rep < 2; ++rep) {
-                if (rep == 1) exp_dep(dwp.x, Fx.z);
-                const V3<Real> pos = dwp;
-#else
-              {
                 const V3<Real>& pos = d.pos;
-#endif
                 // _downwash (BaseAviary.py:792-818): lane ql evaluates partner drones ql, ql + 4 (its
                 // term alpha exp(-(dxy / beta)^2 / 2); 4 dz and beta are > 0 where it is used, dxy
                 // a root of a sum of squares); the quad sums the terms by a DPP butterfly, so every
@@ -1021,7 +978,6 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
                 const Real fz = -tsum;
                 const M3<Real>& Rs = H.link_lag && !(PH == ADRP_PHYS_PYB_GND_DRAG_DW) ? Rl : Rq;
                 Fx = fz * col2(Rs);
-              }
             }
             // disturbances: compile-time (the host runs this kernel with DRAWS = disturbances on and
             // the draws made up front; parity-mode injection and in-loop draws go to the one-lane
@@ -1044,14 +1000,6 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
             }
             CP_MARK(f1);
             CP_ADD(4, f1 - ta);
-#ifdef ADRP_EXP_DUP_STEP
-            {
-                RDrone<Real> d2 = d;
-                M3<Real> Rq2 = Rq, Rl2 = Rl;
-                race_pyb_substep_r<Real, PH>(H, d2, Fx, Tx, Rq2, Rl2);
-                exp_dep(Fx.x, d2.q.x);
-            }
-#endif
             race_pyb_substep_r<Real, PH>(H, d, Fx, Tx, Rq, Rl);
         }
 #ifdef ADRP_RACE_TIMING
@@ -1064,22 +1012,7 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
             for (int k = 0; k < 4; ++k) d.rpm[k] = d.prev[k] = Real(0);
         } else {
             CP_MARK(e0);
-#ifdef ADRP_EXP_DUP_EUL
-            Q4<Real> q2 = d.q;
-            exp_dep(q2.x, euler_axis_q4(d.q, cax));
-            const Real rpy_a = euler_axis_q4(q2, cax);
-#else
             const Real rpy_a = euler_axis_q4(d.q, cax);
-#endif
-#ifdef ADRP_EXP_DUP_WRAP
-            {
-                RDrone<Real> d2 = d;
-                Real prv2 = prv;
-                float l12 = l1, l22 = l2;
-                mellinger_q4(d2, lpf, sp, xc_x, xc_y, rpy_a, prv2, l12, l22, noise_m, ql, Rq CP_ARG);
-                exp_dep(prv, d2.rpm[0]);
-            }
-#endif
             CP_MARK(e1);
             CP_ADD(0, e1 - e0);
             mellinger_q4(d, lpf, sp, xc_x, xc_y, rpy_a, prv, l1, l2, noise_m, ql, Rq CP_ARG);
@@ -1099,10 +1032,7 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
     // (fp64 since round 3: config 4 95 -> 80.5 us; fp32 since round 5, with the auto-reset copying
     // images: config 3 30.4 -> 30.0 us, config 3 + actor 54.5 -> 53.7 us, config 4 unchanged, where
     // rounds 3 and 4 had measured it +0.3-0.5 us)
-    constexpr bool kEarlyStore = true;
-    if constexpr (kEarlyStore) {
-        if (owner) store_drone_body<Real, PH == ADRP_PHYS_DYN>(a, EN, slot, d);
-    }
+    if (owner) store_drone_body<Real, PH == ADRP_PHYS_DYN>(a, EN, slot, d);
     // the episode this env's next-reset image is for, loaded here so that its latency hides behind
     // the post-loop phases (the barrier keeps the load from sinking to its use in the auto-reset)
     const int img_for = a.img_ep != nullptr ? a.img_ep[e] : -2;
@@ -1124,6 +1054,8 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
         Real sn, cs;
         sincos_f_(rotg, &sn, &cs);
         const Real dx = Real(0.05) * cs, dy = Real(0.05) * sn;
+        // (near-mask slack: 1e-5 in both precisions here, 1e-10 in race_step_kernel's fp64: history,
+        // not design; the mask is a conservative pre-filter, so the decision is the same either way)
         const Real br = fabs_(C.coll_zoff) + hsqrt_(C.coll_r * C.coll_r + C.coll_hh * C.coll_hh) + Real(1e-5);
         uint32_t near = 0;
 #pragma unroll
@@ -1271,7 +1203,6 @@ __global__ void __launch_bounds__(kRaceBlock) race_step_q4(RaceArgs<Real> a) {
             a.trunc[e] = tr;
         }
         if (!reset) {
-            if constexpr (!kEarlyStore) store_drone_body<Real, PH == ADRP_PHYS_DYN>(a, EN, slot, d);
             store_drone_flags(a, EN, slot, d);
             a.ist[RI_STEP * EN + slot] = sc0 + C.S;
             if (dn == 0) a.ist[RI_WR_GATE * EN + slot] = wr_gate;

@@ -640,7 +640,9 @@ def test_full_size_subset_vs_oracle(E, N, level, physics, mode, precision):
 @pytest.mark.parametrize("precision", ["fp32", "fp64"])
 @pytest.mark.parametrize("level,N,physics,mode", [("level0", 2, Physics.PYB, RaceMode.COMPARE),
                                                   ("level3", 4, Physics.PYB_DW, RaceMode.COMPETE),
-                                                  ("level2", 3, Physics.PYB_GND_DRAG_DW, RaceMode.COMPETE)])
+                                                  ("level2", 3, Physics.PYB_GND_DRAG_DW, RaceMode.COMPETE),
+                                                  ("level2", 1, Physics.PYB, RaceMode.COMPARE),
+                                                  ("level2", 8, Physics.PYB, RaceMode.COMPETE)])
 @pytest.mark.parametrize("yaw", [False, True])
 def test_quad_matches_lane(monkeypatch, level, N, physics, mode, precision, yaw):
     """the race step in its two layouts, four lanes per drone (default, race_quad.h) and one
