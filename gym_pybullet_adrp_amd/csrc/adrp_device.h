@@ -555,6 +555,78 @@ __device__ __forceinline__ void expmap_sinc_cos(double x, double* sinc, double* 
     *sinc = f64::fma_(x2, ps, 1.0);
     *c = f64::fma_(x2, pc, 1.0);
 }
+// ---- lean f64::atan2 / f64::asin for a wave that has its constants in VGPRs ------------------
+// The hover step's angle helper waves (hover_kernel.h) sit idle until the chain wave hands them its final
+// quaternion, and the chain then waits for their angles: every instruction between is on the step's path.
+// About a quarter of f64::atan2's are the two moves per 64-bit constant, and as many again serve arguments
+// the obs angles meet once in a blue moon.  The lean forms take the constants from an AngK that the wave
+// pinned while it was idle (the ChainK idiom) and assume
+//   atan2_lean: x and y not NaN and max(|x|, |y|) neither tiny nor huge (atan2_lean_ok), so the quotient
+//               needs no zero guard and the reciprocal no non-finite fix-up (rcp_nc: the same bits as
+//               rcp wherever its result is finite); XPOS: x >= 0, no reflection about pi/2
+//   asin_lean:  |s| < 0.99999 (the gimbal threshold), so (1 - s)(1 + s) >= 1e-5 and the square root needs
+//               none of f64::sqrt's zero / negative / infinity selects (sqrt_nn's iteration, without its
+//               clamp: the argument is never near zero)
+// On such arguments they are f64::atan2 / f64::asin operation for operation, so they give the same bits.
+// The caller sends the WHOLE wave to the full functions behind one vote when any lane's arguments are
+// outside (euler_*_lean in hover_kernel.h): no lane ever takes a lean form out of its domain.
+struct AngK {
+    double p[10];                    // atan2_t's polynomial, highest degree first
+    double tan8, pi4, pi2, pi;       // tan(pi/8), pi/4, pi/2, pi
+    double lim, lo, hi;              // 0.99999; the bounds of atan2_lean_ok
+};
+__device__ __forceinline__ AngK ang_consts() {
+    return AngK{{0.021428368220326288, -0.04375458729368037, 0.05699267039194693, -0.06642647883966969,
+                 0.07690277001250925, -0.09090800003785938, 0.11111107550967636, -0.14285714221246087,
+                 0.19999999999459742, -0.3333333333333199},
+                0.41421356237309504880, 0.78539816339744830962, 1.57079632679489661923, 3.14159265358979323846,
+                0.99999, 1e-150, 1e150};
+}
+__device__ __forceinline__ void pin_all(AngK& k) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) pin(k.p[i]);
+    pin(k.tan8); pin(k.pi4); pin(k.pi2); pin(k.pi); pin(k.lim); pin(k.lo); pin(k.hi);
+}
+namespace f64 {
+// |x| + |y| is NaN if either is, and within [max, 2 max]
+__device__ __forceinline__ bool atan2_lean_ok(double y, double x, const AngK& k) {
+    const double s = __builtin_fabs(x) + __builtin_fabs(y);
+    return s > k.lo && s < k.hi;
+}
+template <bool XPOS>
+__device__ __forceinline__ double atan2_lean(double y, double x, const AngK& k) {
+    const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
+    const double mx = __builtin_fmax(ax, ay), mn = __builtin_fmin(ax, ay);
+    const bool big = mn > k.tan8 * mx;
+    const double num = big ? mn - mx : mn, den = big ? mn + mx : mx;
+    const double t = num * rcp_nc(den);
+    const double s = t * t;
+    double p = k.p[0];
+#pragma unroll
+    for (int i = 1; i < 10; ++i) p = fma_(p, s, k.p[i]);
+    double r = fma_(t * s, p, t);
+    if (big) r += k.pi4;
+    if (ay > ax) r = k.pi2 - r;
+    if constexpr (!XPOS) {
+        if (x < 0.0) r = k.pi - r;
+    }
+    return __builtin_copysign(r, y);
+}
+__device__ __forceinline__ double asin_lean(double s, const AngK& k) {
+    const double x = (1.0 - s) * (1.0 + s);
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const double r = fma_(-g, h, 0.5);
+        g = fma_(g, r, g);
+        h = fma_(h, r, h);
+    }
+    const double d = fma_(-g, g, x);
+    return atan2_lean<true>(s, fma_(d, h, g), k);
+}
+}  // namespace f64
+
 __device__ __forceinline__ float quat_inv_norm(float n2, const ChainK<float>&) { return quat_inv_norm(n2); }
 __device__ __forceinline__ double quat_inv_norm(double n2, const ChainK<double>& k) {
     const bool near1 = __builtin_fabs(n2 - 1.0) <= k.near1;

@@ -500,6 +500,28 @@ __device__ __forceinline__ Real euler_yaw_u(Q4<Real> q) {
     return fatan2_(a.y2, a.x2);
 }
 
+// The same three for the fp64 angle helper waves, by the lean forms (adrp_device.h, AngK: the wave's pinned
+// constants).  One vote sends the whole wave to the function above when any lane is outside the lean forms'
+// domain -- NaN, gimbal lock, an atan2 argument pair that is not safely away from zero and infinity -- so
+// every input gives the bits it gives above; on the others the lean forms are the same operations.
+__device__ __forceinline__ double euler_roll_lean(Q4<double> q, const AngK& k) {
+    const EulerArgs<double> a = euler_args(q);
+    const bool ok = fabs_(a.sarg) < k.lim && f64::atan2_lean_ok(a.y0, a.x0, k);
+    if (__builtin_expect(__any(!ok), 0)) return euler_roll_u(q);
+    return f64::atan2_lean<false>(a.y0, a.x0, k);
+}
+__device__ __forceinline__ double euler_pitch_lean(Q4<double> q, const AngK& k) {
+    const double sarg = euler_sarg(q);
+    if (__builtin_expect(__any(!(fabs_(sarg) < k.lim)), 0)) return euler_pitch_u(q);
+    return f64::asin_lean(sarg, k);
+}
+__device__ __forceinline__ double euler_yaw_lean(Q4<double> q, const AngK& k) {
+    const EulerArgs<double> a = euler_args(q);
+    const bool ok = fabs_(a.sarg) < k.lim && f64::atan2_lean_ok(a.y2, a.x2, k);
+    if (__builtin_expect(__any(!ok), 0)) return euler_yaw_u(q);
+    return f64::atan2_lean<false>(a.y2, a.x2, k);
+}
+
 // E = 1 persistent step (SPLIT): lane L evaluates Euler angle min(L, 2) of the (duplicated) env with
 // ONE atan2 -- roll (y0, x0), pitch (sarg, sqrt((1 - sarg)(1 + sarg)), the atan2 form of fasin_),
 // yaw (y2, x2) -- and the three come back by readlane: the same arguments as euler_xyz_fast_u
@@ -952,15 +974,65 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     // rows; with the angle helpers the chain wave takes 3 of the 18, the helpers 5 each
     constexpr int kWaves = HELP ? 1 + help_waves<Real>() : 1;
     constexpr auto cb = [](int w) { return w == 0 ? 0 : (w >= kWaves ? kRowF4 : (kWaves == 2 ? kRowF4 / 2 : 5 * w - 2)); };
+    // TROWS (the ANG kernels): the terminal rows of the done envs leave in two parts.  A done lane of the
+    // chain stores its three kinematic columns from registers (the values it has just staged) and enters
+    // its lane number into done_list at its rank among the done lanes; the count goes to done_cnt.  Behind
+    // barrier B each helper wave copies its five ring columns of those rows from the staged block, twelve
+    // rows per pass over lanes 0..59 (lane l: list entry l / 5, column l % 5): one pass up to twelve done
+    // envs in a block (5.5 at the benched shape), where the chain, one instruction per issue slot, had 15
+    // LDS reads and 15 stores of its own for them.  The ring columns are not touched by a reset, so
+    // they are the terminal row's behind B as before it.
+    constexpr bool TROWS = ANG;
+    constexpr int kSplitCols = 5, kSplitRows = 12;   // ring columns per helper wave, rows per pass
+    static_assert(!TROWS || (cb(2) - cb(1) == kSplitCols && cb(4) - cb(3) == kSplitCols && cb(1) == 3 &&
+                             kSplitCols * kSplitRows <= kStepBlock), "terminal rows: 3 + 3 x 5 columns");
+    __shared__ int done_cnt[1];
+    __shared__ uint8_t done_list[TROWS ? kStepBlock : 1];
+    // A helper wave's work behind barrier B (tl: its lane, wv: its wave): its five columns of the block's obs
+    // copy-out, and its five ring columns of the done envs' terminal rows.  The count, the first pass's list
+    // entry and, through it, the first pass's float4 are read ahead of the copy-out's stores, needed or not
+    // (a list entry past the count is stale: it is masked to a row of the block and not stored), so that
+    // the common single pass adds one predicated store to the wave's tail and no LDS round trip.
+    [[maybe_unused]] auto helper_tail = [&](int tl, int wv) {
+        const int cnt_v = done_cnt[0];
+        const int sub = tl / kSplitCols, c = cb(wv) + tl - kSplitCols * sub;
+        const int row0 = done_list[sub] & (kStepBlock - 1);
+        float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+        float4 o[kSplitCols];
+#pragma unroll
+        for (int j = 0; j < kSplitCols; ++j) o[j] = rows[tl + kStepBlock * (cb(wv) + j)];
+        const float4 t0 = rows[row0 * kRowF4 + c];
+#pragma unroll
+        for (int j = 0; j < kSplitCols; ++j) store_out(dst + tl + kStepBlock * (cb(wv) + j), o[j]);
+        const int cnt = __builtin_amdgcn_readfirstlane(cnt_v);
+        const bool mine = tl < kSplitCols * kSplitRows;
+        float4* tb = reinterpret_cast<float4*>(a.tobs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+        if (mine && sub < cnt) tb[row0 * kRowF4 + c] = t0;
+        for (int base = kSplitRows; base < cnt && base < kStepBlock; base += kSplitRows) {
+            const int n = base + sub;
+            if (mine && n < cnt) {
+                const int row = done_list[n] & (kStepBlock - 1);
+                tb[row * kRowF4 + c] = rows[row * kRowF4 + c];
+            }
+        }
+    };
     if constexpr (HELP) {
         if (ANG && threadIdx.x >= 2 * kStepBlock) {   // angle helpers: pitch (wave 2), yaw (wave 3)
             const int tl = threadIdx.x & (kStepBlock - 1), wv = threadIdx.x / kStepBlock;
+            AngK ak = ang_consts();   // the lean angle forms' constants, into VGPRs while the wave is idle
+            pin_all(ak);
             __syncthreads();   // A: the chain's final quaternion
             const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
-            if (wv == 2) ang_p[tl] = euler_pitch_u(q);
-            else ang_y[tl] = float(euler_yaw_u(q));
+            if constexpr (ANG) {   // (this branch is the ANG kernels' alone; fp32 has no lean forms to compile)
+                if (wv == 2) ang_p[tl] = euler_pitch_lean(q, ak);
+                else ang_y[tl] = float(euler_yaw_lean(q, ak));
+            }
             __syncthreads();   // C: pitch and yaw
             __syncthreads();   // B: the final rows
+            if constexpr (TROWS) {
+                helper_tail(tl, wv);
+                return;
+            }
             float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
             for (int k = cb(wv); k < cb(wv + 1); ++k) store_out(dst + tl + kStepBlock * k, rows[tl + kStepBlock * k]);
             return;
@@ -1016,13 +1088,19 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                 }
             }
             reinterpret_cast<float4*>(a.ring)[size_t(head) * E + he] = av;
+            [[maybe_unused]] AngK ak = ang_consts();   // (ANG: pinned behind this wave's reset work, before A)
+            if constexpr (ANG) pin_all(ak);
             __syncthreads();   // A: reset states and ring rows in LDS
             if constexpr (ANG) {   // this wave is idle from here to the copy-out: it takes the roll
                 const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
-                ang_r[tl] = euler_roll_u(q);
+                ang_r[tl] = euler_roll_lean(q, ak);
                 __syncthreads();   // C
             }
             __syncthreads();   // B: the chain wave's kinematic parts and reset rows
+            if constexpr (TROWS) {
+                helper_tail(tl, 1);
+                return;
+            }
             // this wave's part of the block's coalesced copy-out
             float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
 #pragma unroll
@@ -1258,8 +1336,20 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
         my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
         if constexpr (HELP && !ANG) __syncthreads();   // A: the helper wave's reset states
+        if constexpr (TROWS) {   // (every lane writes the same word)
+            const unsigned long long done_mask = __ballot(done);
+            done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;
+            if (done && a.tobs) {   // terminal obs: the kinematic columns from here, the ring columns by the helpers
+                float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(e) * D);
+                trow[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
+                trow[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
+                trow[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(uint32_t(done_mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(done_mask), 0u));
+                done_list[rank] = uint8_t(threadIdx.x);
+            }
+        }
         if (done) {
-            if (a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
+            if (!TROWS && a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
                 float4 t[kRowF4];
 #pragma unroll
                 for (int k = 0; k < kRowF4; ++k) t[k] = my[k];
