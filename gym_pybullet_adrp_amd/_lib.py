@@ -158,6 +158,26 @@ def load():
     lib.adrp_dslpid_compute.restype = I
     lib.adrp_dslpid_compute_env.argtypes = [P, ctypes.c_double, P, P, P, P, P, P, P, P, P]
     lib.adrp_dslpid_compute_env.restype = I
+    if hasattr(lib, "adrp_mellinger_create"):   # (A/B runs load the parent commit's build, which has none)
+        lib.adrp_mellinger_create.argtypes = [I, I, I, ctypes.POINTER(P)]
+        lib.adrp_mellinger_create.restype = I
+        lib.adrp_mellinger_destroy.argtypes = [P]
+        lib.adrp_mellinger_destroy.restype = None
+        lib.adrp_mellinger_reset.argtypes = [P, P, P, P, P, P]
+        lib.adrp_mellinger_reset.restype = I
+        lib.adrp_mellinger_command.argtypes = [P, P, P, P]
+        lib.adrp_mellinger_command.restype = I
+        lib.adrp_mellinger_compute.argtypes = [P, P, P, P, I, I, P, P, P]
+        lib.adrp_mellinger_compute.restype = I
+        lib.adrp_mellinger_compute_env.argtypes = [P, P, P, P, P, P]
+        lib.adrp_mellinger_compute_env.restype = I
+        lib.adrp_mellinger_state_layout.argtypes = [P, ctypes.POINTER(I), ctypes.POINTER(I)]
+        lib.adrp_mellinger_state_layout.restype = I
+        lib.adrp_mellinger_state_field.argtypes = [I, I]
+        lib.adrp_mellinger_state_field.restype = ctypes.c_char_p
+        for name in ("get_state", "set_state", "get_command_state", "set_command_state"):
+            getattr(lib, f"adrp_mellinger_{name}").argtypes = [P, P, P, P]
+            getattr(lib, f"adrp_mellinger_{name}").restype = I
     lib.adrp_compact_rows.argtypes = [P, P, P, I, I, I, P, P, P, P]
     lib.adrp_compact_rows.restype = I
     lib.adrp_memcpy_async.argtypes = [P, P, ctypes.c_size_t, I, P]

@@ -181,6 +181,20 @@ inline const CtrlConst<Real>* ctrl_const(const adrp_t* h) {
 }
 inline bool is_ctrl_task(int task) { return task == ADRP_TASK_CTRL || task == ADRP_TASK_VELOCITY; }
 
+// lpf2pInit(gyrolpf, 500, 30): the firmware's filter.c in C float (host libm, no contraction: the same
+// values the oracle's restatement computes); b0, b1, b2, a1, a2
+inline void race_gyro_lpf(float out[5]) {
+#pragma clang fp contract(off)
+    const float fr = 500.0f / 30.0f;
+    const float ohm = tanf(3.14159265358979323846f / fr);
+    const float cc = 1.0f + 2.0f * cosf(3.14159265358979323846f / 4.0f) * ohm + ohm * ohm;
+    out[0] = ohm * ohm / cc;
+    out[1] = 2.0f * out[0];
+    out[2] = out[0];
+    out[3] = 2.0f * (ohm * ohm - 1.0f) / cc;
+    out[4] = (1.0f - 2.0f * cosf(3.14159265358979323846f / 4.0f) * ohm + ohm * ohm) / cc;
+}
+
 template <typename Real>
 constexpr size_t race_ticks_offset() { return (sizeof(RaceConst<Real>) + 255) & ~size_t(255); }
 

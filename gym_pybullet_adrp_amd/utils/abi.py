@@ -32,6 +32,7 @@ POLICY_TANH, POLICY_RELU = 0, 1
 POLICY_RAW, POLICY_RELATIVE, POLICY_ABSOLUTE = 0, 1, 2
 VEC_SLOTS = 4   # ADRP_VEC_SLOTS
 DSLPID_CF2X, DSLPID_CF2P = 0, 1
+CMD_NF, CMD_NI, CMD_ARGS = 63, 3, 14   # ADRP_CMD_NF / _NI / _ARGS (command state, adrp_mellinger_*)
 RACE_CTRL_NONE, RACE_CTRL_HARDCODED, RACE_CTRL_POLICY = 0, 1, 2
 
 _d = ctypes.c_double

@@ -714,6 +714,64 @@ int adrp_dslpid_compute_env(adrp_dslpid_t* c, double control_timestep, adrp_t* h
                             const void* target_rpy_dev, const void* target_vel_dev, const void* target_rpy_rates_dev,
                             void* rpm_out, void* pos_e_out, void* yaw_e_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Stand-alone batched MellingerControl (control/MellingerControl.py:17-699): the Crazyflie firmware
+ * controller that examples/cf.py / CFAviary step at 500 Hz, for users who drive CtrlAviary themselves.
+ * One handle holds `rows` independent controllers (row e * N + n): the wrapper state and the firmware's
+ * in the handle's precision, the high-level commander's as adrp_get_command_state describes it.  Every
+ * call is one kernel launch on the caller's stream, without allocation or host synchronisation
+ * (capturable).  The controller code is the race step kernels' (csrc/race_kernel.h mellinger_compute,
+ * csrc/commander.h); csrc/mellinger_kernel.h only moves a row's state in and out.
+ *
+ * There is no command queue: adrp_mellinger_command processes its message at once, as the reference's
+ * low_level_control does (send*Cmd, then process_command_queue(args[-1])).
+ *
+ * Errors of these calls are reported through adrp_last_error(NULL).  Argument errors (rows <= 0,
+ * precision not 0 / 1, NULL pointers, a negative stride) are refused before any device call.
+ * --------------------------------------------------------------------------------------- */
+typedef struct adrp_mellinger adrp_mellinger_t;
+int adrp_mellinger_create(int rows, int precision, int device, adrp_mellinger_t** out);
+void adrp_mellinger_destroy(adrp_mellinger_t* c);
+/* MellingerControl.reset(init_obs) (:99-150) of all rows (mask_dev NULL) or of the rows with
+ * mask_dev[r] != 0 (uint8 [rows]): filters, integrators, histories, tick, last_*_tick, tumble and the
+ * last controls / rpm cleared, prev_rpy / prev_vel from the given rows, the setpoint zeroed with the
+ * override on, the commander idle and told the state (position, yaw; at rest).  pos / rpy / vel:
+ * packed [rows][3] in the handle's precision.  Other rows are left alone. */
+int adrp_mellinger_reset(adrp_mellinger_t* c, const void* pos_dev, const void* rpy_dev, const void* vel_dev,
+                         const uint8_t* mask_dev, void* stream);
+/* One command message per row, packed as for adrp_race_command: codes_dev int32 [rows] ADRP_CMD_*,
+ * args_dev float64 [rows][ADRP_CMD_ARGS]; ADRP_CMD_NONE leaves a row untouched. */
+int adrp_mellinger_command(adrp_mellinger_t* c, const int32_t* codes_dev, const double* args_dev, void* stream);
+/* MellingerControl.computeControl (:154-262) of every row, once.  pos / rpy / vel: component k of row r is
+ * base[r * row_stride + k]; row_stride 0 means three packed arrays [rows][3], and rows of
+ * _getDroneStateVector's layout [rows][20] are passed as row, row + 7, row + 10 with row_stride 20.
+ * input_precision is the element type of the three (0 float32, 1 float64): the handle's own, or float32
+ * into a float64 handle (converted on load).  disturbance_dev: [rows][4] in the handle's precision, the
+ * per-motor thrust disturbance the reference passes in the target_pos slot, NULL = zeros.  rpm_out:
+ * [rows][4] in the handle's precision (what adrp_step_rpm takes). */
+int adrp_mellinger_compute(adrp_mellinger_t* c, const void* pos_dev, const void* rpy_dev, const void* vel_dev,
+                           int row_stride, int input_precision, const void* disturbance_dev, void* rpm_out,
+                           void* stream);
+/* The same with pos / vel read from the state columns of CtrlAviary handle h and roll / pitch / yaw taken
+ * from its quaternion columns by the race kernels' Euler function; rpy_out ([rows][3], handle precision)
+ * receives those angles, or is NULL.  Refused: a handle of another task, one whose E * N, precision or
+ * device differs from the controller's. */
+int adrp_mellinger_compute_env(adrp_mellinger_t* c, adrp_t* h, const void* disturbance_dev, void* rpm_out,
+                               void* rpy_out, void* stream);
+/* Controller state: nf float fields (handle precision) and ni int32 fields, each a contiguous [rows]
+ * vector; the names are those of the race state's controller part (adrp_state_field of a race handle):
+ * rpm_*, prev_rpm_*, prev_rpy_*, prev_vel_*, lpf_d1_*, lpf_d2_*, i_err_*, i_err_m_*, prev_omega_roll /
+ * pitch, prev_sp_roll / pitch, ctl_roll / pitch / yaw / thrust (the int16 moments of the last firmware
+ * call); tick, last_att_tick, last_pos_tick, tumble.  A negative tick counts as 0.  The layout is the
+ * same for every handle: adrp_mellinger_state_layout takes NULL for c as well. */
+int adrp_mellinger_state_layout(const adrp_mellinger_t* c, int* nf, int* ni);
+const char* adrp_mellinger_state_field(int is_int, int index);
+int adrp_mellinger_get_state(adrp_mellinger_t* c, void* f_dev, int32_t* i_dev, void* stream);
+int adrp_mellinger_set_state(adrp_mellinger_t* c, const void* f_dev, const int32_t* i_dev, void* stream);
+/* float [ADRP_CMD_NF][rows], int32 [ADRP_CMD_NI][rows], as adrp_get_command_state */
+int adrp_mellinger_get_command_state(adrp_mellinger_t* c, float* f_dev, int32_t* i_dev, void* stream);
+int adrp_mellinger_set_command_state(adrp_mellinger_t* c, const float* f_dev, const int32_t* i_dev, void* stream);
+
 /* SB3 VecEnv host path: the terminal observations of the finished envs, compacted on the device
  * behind the step's packed outputs so ONE device -> host copy returns them (replaces the per-env
  * infos[e]["terminal_observation"] = obs that stable_baselines3 DummyVecEnv.step_wait fills from
