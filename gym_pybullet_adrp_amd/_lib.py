@@ -138,6 +138,13 @@ def load():
     lib.adrp_race_results_step.restype = I
     lib.adrp_race_results_step_env.argtypes = [P, P, P, P, P, P]
     lib.adrp_race_results_step_env.restype = I
+    if hasattr(lib, "adrp_race_agents_step"):   # (A/B runs load the parent commit's build, which has none)
+        lib.adrp_race_agents_reset.argtypes = [P, P, P, P]
+        lib.adrp_race_agents_reset.restype = I
+        lib.adrp_race_agents_step.argtypes = [P, P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
+        lib.adrp_race_agents_step.restype = I
+        lib.adrp_race_agents_step_env.argtypes = [P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
+        lib.adrp_race_agents_step_env.restype = I
     lib.adrp_race_plan.argtypes = [P, P]
     lib.adrp_race_plan.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]

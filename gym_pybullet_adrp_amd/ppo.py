@@ -143,22 +143,44 @@ class PPOLearner:
         """``n_epochs`` passes over the collector's T x E samples, each a fresh random permutation cut
         into consecutive slices of ``batch_size`` (the last one shorter), as RolloutBuffer.get yields
         them.  ``permutations``: int64 [n_epochs, T E] to use instead of ``torch.randperm``.  Returns
-        the statistics [n_epochs, n_minibatches, 5] (device tensor; nothing is read back)."""
+        the statistics [n_epochs, n_minibatches, 5] (device tensor; nothing is read back).
+
+        A collector with a ``valid`` attribute (``MultiAgentRolloutCollector``: [T, E] uint8, 0 for the samples
+        of a drone whose agent episode is over) is trained on its valid rows only: each epoch permutes the
+        n_valid flat indices of those rows (one ``torch.nonzero`` per call, the call's one host read), and
+        ``permutations`` is then int64 [n_epochs, n_valid] of such indices."""
         if target_kl is not None:
             raise ValueError("target_kl early stopping needs a host read per minibatch and is not implemented")
         n = col.T * col.E
         flat = (col.obs.view(n, -1), col.actions.view(n, -1), col.values.view(n), col.log_probs.view(n),
                 col.advantages.view(n), col.returns.view(n))
+        # the index pool: every row, or the valid ones (no index of another row reaches ``update``)
+        rows, pool, what = None, n, str(n)
+        if getattr(col, "valid", None) is not None:
+            valid = col.valid.view(n) != 0
+            rows = torch.nonzero(valid).view(-1)              # int64, ascending; the host learns n_valid here
+            pool, what = rows.numel(), f"n_valid = {rows.numel()}"
+            if pool == 0:
+                raise ValueError("the rollout holds no valid sample")
         if permutations is not None:
             permutations = permutations.to(device=self.device, dtype=torch.int64).contiguous()
-            if tuple(permutations.shape) != (self.n_epochs, n):
-                raise ValueError(f"permutations must be [n_epochs, {n}]")
-        nmb = (n + self.batch_size - 1) // self.batch_size
+            if tuple(permutations.shape) != (self.n_epochs, pool):
+                raise ValueError(f"permutations must be [n_epochs, {what}]")
+            if rows is not None:
+                inside = (permutations >= 0) & (permutations < n)
+                if not bool((inside & valid[permutations.clamp(0, n - 1)]).all()):
+                    raise ValueError("permutations holds the index of an invalid row")
+        nmb = (pool + self.batch_size - 1) // self.batch_size
         stats = torch.zeros((self.n_epochs, nmb, 5), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             for e in range(self.n_epochs):
-                perm = permutations[e] if permutations is not None else torch.randperm(n, device=self.device, generator=self._gen)
-                for k, s in enumerate(range(0, n, self.batch_size)):
+                if permutations is not None:
+                    perm = permutations[e]
+                else:
+                    perm = torch.randperm(pool, device=self.device, generator=self._gen)
+                    if rows is not None:
+                        perm = rows[perm]
+                for k, s in enumerate(range(0, pool, self.batch_size)):
                     self.update(*flat, perm[s:s + self.batch_size], stats=stats[e, k])
         return stats
 

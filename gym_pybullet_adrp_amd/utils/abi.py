@@ -186,6 +186,17 @@ class AdrpRaceResultsIO(ctypes.Structure):
                 ("log_gates", _p), ("log_finish", _p), ("log_elim", _p)]
 
 
+AGENTS_OBS_MIN = 49                                    # ADRP_AGENTS_OBS_MIN
+
+
+class AdrpRaceAgentsIO(ctypes.Structure):
+    """adrp_race_agents_io (include/adrp.h): the caller-owned device buffers of the per-drone race agents"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("obs_dim", _i32),
+                ("num_gates", _i32), ("reserved", _i32),
+                ("wr_gate", _p), ("wr_target", _p), ("wr_prev", _p), ("alive", _p), ("run_return", _p), ("run_length", _p)]
+
+
 PLAN_KNOTS, PLAN_COEF, PLAN_OBS_MIN = 20, 16, 28       # ADRP_PLAN_*
 PLAN_NOT_IER0, PLAN_CEILING = 1, 2                     # adrp_race_plan status bits 0 / 1; n in bits 8..15, iterations 16..23
 

@@ -608,6 +608,67 @@ int adrp_race_results_step_env(const adrp_race_results_io* io, adrp_t* h, const 
                                const uint8_t* trunc, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-drone PPO agents of a multi-drone race (rollout.MultiAgentRolloutCollector): the bookkeeping that makes
+ * every drone of a MultiRaceAviary(autoreset = 0) its own agent, one small launch per env.step.  One lane per
+ * agent slot j = e * N + n.  csrc/agents_kernel.h.  Handle-less like the episode statistics: the caller owns
+ * every buffer (all on one device), every pointer is fixed per step.  No atomics: equal inputs give equal bits.
+ *
+ * adrp_race_agents_reset: for every slot of an env with mask[e] != 0 (mask uint8 [E]; NULL: every env),
+ * utils/wrapper.py RewardWrapper.reset per drone from the drone's own observation row obs + j * D (float32):
+ * wr_gate = (int)row[48], wr_target = row[12:15], wr_prev = row[0:3], alive = 1, run_return = 0, run_length = 0.
+ *
+ * adrp_race_agents_step: after env.step, on the step's obs rows, the per-drone gate / flags int32 [E*N] of the
+ * race state (bit 0 eliminated, bit 1 finished), the env's term / trunc uint8 [E] and boot_value float32 [E*N]
+ * (the critic's values of the post-step rows).  Per slot:
+ *   was_alive = alive; done_now = (flags & 3) != 0; newly = was_alive && done_now; fin = (flags & 2) != 0.
+ *   r = RewardWrapper._compute_reward (wrapper.py:121-186) of this drone, float64 arithmetic on the float32 row:
+ *       gate > wr_gate % 4: wr_gate = gate, r_passed = 5, and wr_target = row[12 + 4 gate : 15 + 4 gate] when
+ *       gate < 4 && gate < num_gates;  r_col = -1 when newly && !fin;  r_lap = 10 when newly && fin;
+ *       r = (|target - prev|_xy - |target - row|_xy) + (|target - prev|_z - |target - row|_z) + r_passed + r_col
+ *       + r_lap (L2 in xy, L1 in z);  wr_prev = row[0:3].  The reference's env-level terminated / task_completed
+ *       are the drone's own "became done" / "finished": with N = 1 it is the fused wrapper's reward.
+ *   boot = was_alive && !done_now && trunc[e] && !term[e] (the time-limit bootstrap of SB3's collect_rollouts).
+ *   rewards[j]    = was_alive ? (float)(r + (boot ? gamma * boot_value[j] : 0)) : 0   (selects: a dead slot's
+ *                   row and a stale boot_value never reach a reward, whatever they hold)
+ *   valid[j]      = was_alive
+ *   next_start[j] = done_now || term[e] || trunc[e] ? 1 : 0
+ *   ep_return[j], ep_length[j] = run_return + r, run_length + 1 where newly || (was_alive && (term[e] | trunc[e])):
+ *                   the agent episode that ends here, without the bootstrap; NaN, 0 elsewhere
+ *   alive = was_alive && !done_now.  wr_gate / wr_target / wr_prev / run_return / run_length change only where
+ *   was_alive: a dead slot keeps its state until its env's adrp_race_agents_reset.
+ * adrp_race_agents_step_env reads gate / flags from handle h's own device image in place.
+ *
+ * Errors are reported through adrp_last_error(NULL).  Refused with ADRP_ERR_INVALID before any device call:
+ * a NULL io, a struct_size mismatch, num_envs < 1, num_drones outside 1..ADRP_MAX_DRONES, obs_dim < 49,
+ * num_gates outside 0..ADRP_MAX_GATES, num_envs * num_drones * obs_dim past 2^31 - 1, a NULL buffer of the io,
+ * NULL obs / gate / flags / term / trunc / boot_value / rewards / valid / next_start / ep_return / ep_length,
+ * a NULL or non-race handle, a handle whose E, N, D differ from the io's.
+ * --------------------------------------------------------------------------------------- */
+#define ADRP_AGENTS_OBS_MIN 49      /* floats of an observation row the agents kernels read from (gate id at 48) */
+typedef struct adrp_race_agents_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_agents_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  obs_dim;         /* D >= ADRP_AGENTS_OBS_MIN floats per (env, drone) row */
+    int32_t  num_gates;       /* 0..ADRP_MAX_GATES (adrp_track.num_gates) */
+    int32_t  reserved;
+    int32_t* wr_gate;         /* [E*N] RewardWrapper.current_gate_id */
+    double*  wr_target;       /* [E*N][3] RewardWrapper.current_target */
+    double*  wr_prev;         /* [E*N][3] RewardWrapper.previous_pos */
+    uint8_t* alive;           /* [E*N] the agent's episode is running */
+    double*  run_return;      /* [E*N] sum of the raw rewards of the running agent episode */
+    int32_t* run_length;      /* [E*N] */
+} adrp_race_agents_io;
+int adrp_race_agents_reset(const adrp_race_agents_io* io, const float* obs, const uint8_t* mask, void* stream);
+int adrp_race_agents_step(const adrp_race_agents_io* io, const float* obs, const int32_t* gate, const int32_t* flags,
+                          const uint8_t* term, const uint8_t* trunc, const float* boot_value, double gamma,
+                          float* rewards, uint8_t* valid, float* next_start, double* ep_return, int32_t* ep_length,
+                          void* stream);
+int adrp_race_agents_step_env(const adrp_race_agents_io* io, adrp_t* h, const float* obs, const uint8_t* term,
+                              const uint8_t* trunc, const float* boot_value, double gamma, float* rewards,
+                              uint8_t* valid, float* next_start, double* ep_return, int32_t* ep_length, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device spline planner of the scripted racer (user_controller/HardCodedController.py:63-115: 16 waypoints
  * from the drone's start and the nominal gates, scipy splprep(s = 0.1), splev at L parameter values): what
  * hardcoded.plan computes per drone on the host, for every (env, drone) of a wave in one launch.
