@@ -145,6 +145,15 @@ def load():
         lib.adrp_race_agents_step.restype = I
         lib.adrp_race_agents_step_env.argtypes = [P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
         lib.adrp_race_agents_step_env.restype = I
+    if hasattr(lib, "adrp_race_roster_act"):    # (likewise)
+        lib.adrp_race_roster_act.argtypes = [P, P]
+        lib.adrp_race_roster_act.restype = I
+        lib.adrp_race_roster_tick.argtypes = [P, P, P]
+        lib.adrp_race_roster_tick.restype = I
+        lib.adrp_race_roster_step.argtypes = [P, P, P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
+        lib.adrp_race_roster_step.restype = I
+        lib.adrp_race_roster_step_env.argtypes = [P, P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
+        lib.adrp_race_roster_step_env.restype = I
     lib.adrp_race_plan.argtypes = [P, P]
     lib.adrp_race_plan.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]

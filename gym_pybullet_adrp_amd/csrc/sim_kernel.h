@@ -17,65 +17,22 @@
 #include <stdint.h>
 
 #include "../../include/adrp.h"
+#include "race_slot.h"
 
 namespace adrp {
 
 constexpr int kCtrlLanes = 256;
 constexpr int kResLanes = 1024, kResWaves = kResLanes / 64;
-constexpr double kHardCtrlFreq = 25.0;   // the scripted controller's own clock (utils/constants.py:31), not the env's
 
-// One lane per (env, drone) slot e * N + n.  Every slot of codes / args is written on every step.
+// One lane per (env, drone) slot e * N + n.  Every slot of codes / args is written on every step (race_slot.h:
+// the body, shared with the roster collector's act kernel, which takes the episode time per env).
 __global__ void __launch_bounds__(kCtrlLanes) race_controller_kernel(adrp_race_ctrl_io io, double ep_time) {
     const int E = io.num_envs, N = io.num_drones, EN = E * N;
     const int slot = blockIdx.x * kCtrlLanes + threadIdx.x;
     if (slot >= EN) return;
     const int e = slot / N, n = slot - e * N;
-    const int kind = io.kind[n];
-    int code = ADRP_CMD_NONE;
-    double a[ADRP_CMD_ARGS];
-#pragma unroll
-    for (int k = 0; k < ADRP_CMD_ARGS; ++k) a[k] = 0.0;
-    if (kind == ADRP_RACE_CTRL_HARDCODED) {
-        // HardCodedCommander.predict (hardcoded.py): step = clamp(int(ep_time * 25) - offset, 0, L)
-        const int L = io.ref_len;
-        const long long it = (long long)__builtin_trunc(ep_time * kHardCtrlFreq);
-        long long st = it - (long long)io.offset[slot];
-        st = st < 0 ? 0 : (st > L ? L : st);
-        const bool took = io.phase[slot] != 0, notified = io.phase[EN + slot] != 0, landed = io.phase[2 * EN + slot] != 0;
-        const bool fst = took && st < L;
-        const bool ntf = took && !fst && !notified;
-        const bool lnd = took && !fst && notified && !landed;
-        if (!took) {                       // TAKEOFF [0.3, 2]; the commander clock is args[-1] = 2
-            code = ADRP_CMD_TAKEOFF;
-            a[0] = 0.3; a[1] = 2.0; a[ADRP_CMD_TIME_SLOT] = 2.0;
-            io.phase[slot] = 1;
-        } else if (fst) {                  // FULLSTATE (ref[step], 0, 0.5 * ones(3), 0, 0, ep_time)
-            const double* __restrict__ r = io.ref + (size_t(slot) * L + size_t(st)) * 3;
-            code = ADRP_CMD_FULLSTATE;
-            a[0] = r[0]; a[1] = r[1]; a[2] = r[2];
-            a[6] = 0.5; a[7] = 0.5; a[8] = 0.5;
-            a[ADRP_CMD_TIME_SLOT] = ep_time;
-        } else if (ntf) {                  // NOTIFY [ep_time]
-            code = ADRP_CMD_NOTIFY;
-            a[0] = ep_time; a[ADRP_CMD_TIME_SLOT] = ep_time;
-            io.phase[EN + slot] = 1;
-        } else if (lnd) {                  // LAND [0, 2]
-            code = ADRP_CMD_LAND;
-            a[1] = 2.0; a[ADRP_CMD_TIME_SLOT] = 2.0;
-            io.phase[2 * EN + slot] = 1;
-        }
-    } else if (kind == ADRP_RACE_CTRL_POLICY) {
-        // RLController._action_transform: [action[:3], ZERO3, ZERO3, action[3], ZERO3, self.time]
-        const float4 s = reinterpret_cast<const float4*>(io.setpoints)[size_t(n) * E + e];
-        code = ADRP_CMD_FULLSTATE;
-        a[0] = double(s.x); a[1] = double(s.y); a[2] = double(s.z);
-        a[9] = double(s.w);
-        a[ADRP_CMD_TIME_SLOT] = ep_time;
-    }
-    io.codes[slot] = code;
-    double2* __restrict__ out = reinterpret_cast<double2*>(io.args + size_t(slot) * ADRP_CMD_ARGS);   // 112-byte rows
-#pragma unroll
-    for (int k = 0; k < ADRP_CMD_ARGS / 2; ++k) out[k] = make_double2(a[2 * k], a[2 * k + 1]);
+    const float4* sp = io.kind[n] == ADRP_RACE_CTRL_POLICY ? reinterpret_cast<const float4*>(io.setpoints) + (size_t(n) * E + e) : nullptr;
+    race_controller_slot(slot, EN, io.kind[n], sp, io.ref_len, io.ref, io.offset, io.phase, ep_time, io.codes, io.args);
 }
 
 // Fixed-order count over one workgroup: wave shuffles, then the sixteen wave sums in index order.

@@ -85,6 +85,7 @@ class DevicePolicy:
             raise ValueError("RLController transforms need the 4 outputs (x, y, z, yaw)")
         self.in_dim, self.h1, self.h2 = w1.shape[1], w1.shape[0], w2.shape[0]
         self.mode = MODES[mode]
+        self.activation = "relu" if activation == "relu" else "tanh"
         self.device = torch.device("cuda", device)
         self._w = w                                  # keep the host arrays alive during create
         h = ctypes.c_void_p()

@@ -93,6 +93,17 @@ class PPOLearner:
         self._check(self.lib.adrp_ppo_params(self.h, p.data_ptr(), None, None, None, self._stream()), "adrp_ppo_params")
         return self._split(p)
 
+    def snapshot(self, mode=None):
+        """a new frozen ``DevicePolicy`` of the actor as it is now (its weights from ``state_dict()``, the learner
+        policy's activation, its mode unless ``mode`` names another): later updates, which rewrite the learner
+        policy in place, do not move it.  A self-play opponent for ``RosterRolloutCollector`` / ``simulate()``;
+        the caller closes it."""
+        from .policy import MODES, DevicePolicy
+        sd = self.state_dict()
+        if mode is None:
+            mode = next(k for k, v in MODES.items() if v == self.policy.mode)
+        return DevicePolicy({k: sd[k].cpu().numpy() for k in ACTOR_KEYS}, self.policy.activation, self.device.index, mode)
+
     def load_state_dict(self, sd):
         p = self._join(sd)
         self._check(self.lib.adrp_ppo_set_params(self.h, p.data_ptr(), None, None, -1, self._stream()), "adrp_ppo_set_params")

@@ -26,6 +26,10 @@ fixed per step).
 per-agent bookkeeping (the RewardWrapper per drone, a drone's own episode end while its env goes on, the
 validity of a dead drone's samples, the bootstrap, the episode starts) in one ``adrp_race_agents_step``
 launch per step (csrc/agents_kernel.h).
+
+``RosterRolloutCollector`` adds opponents to it: a roster gives every drone a role (the learner, the scripted
+``HardCodedController``, a frozen policy, none), only the learner drones have buffer columns, and every drone is
+driven through the env's command path on its own env's episode clock (csrc/roster_kernel.h).
 """
 import ctypes
 
@@ -292,3 +296,203 @@ class MultiAgentRolloutCollector:
         k = int(out[0])
         return {"ep_rew_mean": out[1] / k if k else float("nan"), "ep_len_mean": out[2] / k if k else float("nan"),
                 "episodes": k}
+
+
+class RosterRolloutCollector(MultiAgentRolloutCollector):
+    """Per-drone PPO rollouts of a multi-drone race against opponents: ``roster`` gives every drone one role,
+    ``"learner"`` (a sample of ``policy``, the one being trained), ``"hardcoded"`` (the scripted
+    HardCodedController, delay = drone index as ``sim.ControllerBank``), a frozen ``DevicePolicy`` in mode
+    "relative" / "absolute" (e.g. ``PPOLearner.snapshot()``: self-play) or ``None`` (the drone gets Command.NONE).
+
+    Only the L learner drones have buffer columns: ``E`` = L x num_envs, column ``l * num_envs + e`` is learner l
+    (the l-th "learner" entry of the roster) in env e, drone-major.  ``T``, ``E``, the flat buffers, ``valid``,
+    ``ep_return`` / ``ep_length`` and ``episode_summary()`` are ``MultiAgentRolloutCollector``'s, so
+    ``PPOLearner.train(col)`` works unchanged.  The env must be a ``MultiRaceAviary(autoreset=False,
+    commands=True)``: every step goes through the command path ``simulate()`` evaluates the agent under, with the
+    episode time of each env's own clock.  Per step next to ``env.step``: L strided row copies, one sampling
+    launch over the L E compact rows, one ``adrp_policy_act`` per frozen drone, and the three roster launches
+    (csrc/roster_kernel.h).  ``collect`` makes no host read.
+
+    The scripted drones plan once, in ``reset()``, from the reset observation (``planner``: "host" or "device");
+    an env reset during a rollout restarts its scripted drones' clock and phases but does not re-plan."""
+
+    def __init__(self, env, policy, roster, n_steps, gamma=0.99, gae_lambda=0.95, seed=0, planner="host"):
+        from .policy import MODES, DevicePolicy
+        if not isinstance(env, MultiRaceAviary):
+            raise ValueError("a roster is collected from a MultiRaceAviary")
+        if env.cfg.autoreset:
+            raise ValueError("a roster needs MultiRaceAviary(autoreset=False): the collector resets the finished envs "
+                             "itself, after the agents' step")
+        if not env.commands:
+            raise ValueError("a roster needs MultiRaceAviary(commands=True): every drone is driven through the command path")
+        if planner not in ("host", "device"):
+            raise ValueError(f"planner must be 'host' or 'device', not {planner!r}")
+        if not policy.has_critic:
+            raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
+        D, A = env.h.D, policy.act_dim
+        if A != 4:
+            raise ValueError("a race agent's policy emits the 4 FULLSTATE outputs (x, y, z, yaw)")
+        if policy.in_dim > D:
+            raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
+        self.num_envs, self.N = env.num_envs, env.NUM_DRONES
+        roster = list(roster)
+        if len(roster) != self.N:
+            raise ValueError(f"the roster has {len(roster)} entries for {self.N} drones: give one per drone")
+        dev = env.device
+        self.roles, self.learners, self._frozen = [], [], []
+        for n, c in enumerate(roster):
+            if c is None or (isinstance(c, str) and c.lower() == "none"):
+                self.roles.append(abi.ROSTER_NONE)
+            elif isinstance(c, str) and c.lower() == "hardcoded":
+                self.roles.append(abi.ROSTER_HARDCODED)
+            elif isinstance(c, str) and c.lower() == "learner":
+                self.roles.append(abi.ROSTER_LEARNER)
+                self.learners.append(n)
+            elif isinstance(c, DevicePolicy):
+                if c.mode == MODES["raw"] or c.act_dim != 4:
+                    raise ValueError(f"drone {n}: a race policy emits a setpoint (mode 'relative' or 'absolute', 4 outputs)")
+                if c.in_dim > D:
+                    raise ValueError(f"drone {n}: the policy reads {c.in_dim} inputs, a drone's observation row has {D}")
+                if c.device != dev:
+                    raise ValueError(f"drone {n}: the policy lives on {c.device}, the env on {dev}")
+                self.roles.append(abi.ROSTER_POLICY)
+                self._frozen.append((n, c))
+            else:
+                raise ValueError(f"drone {n}: not a roster entry: {c!r} ('learner', 'hardcoded', a DevicePolicy or None)")
+        if not self.learners:
+            raise ValueError("the roster has no 'learner' drone: nothing to collect")
+        self.env, self.policy, self.roster, self.planner = env, policy, roster, planner
+        self.L = len(self.learners)
+        self.T, self.E = int(n_steps), self.L * self.num_envs
+        self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
+        T, R, E, N = self.T, self.E, self.num_envs, self.N
+        f32 = dict(dtype=torch.float32, device=dev)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.obs = torch.zeros((T, R, D), **f32)
+        self.actions = torch.zeros((T, R, A), **f32)
+        self.rewards, self.episode_starts, self.values, self.log_probs, self.advantages, self.returns = \
+            (torch.zeros((T, R), **f32) for _ in range(6))
+        self.valid = z((T, R), torch.uint8)
+        self.ep_return, self.ep_length = z((T, R), torch.float64), z((T, R), torch.int32)
+        self._post = torch.zeros((R, D), **f32)            # the learner rows after the step, compact
+        self._last_start = torch.ones(R, **f32)
+        self.last_values, self.last_dones, self._tv = (torch.zeros(R, **f32) for _ in range(3))
+        self._scratch = (torch.zeros((R, 4), **f32), torch.zeros((R, A), **f32), torch.zeros(R, **f32))
+        self._mask = z(E, torch.bool)
+        # per-agent state (adrp_race_agents_io): all E N slots, the learner drones' are used
+        S = E * N
+        self.wr_gate, self.run_length = z(S, torch.int32), z(S, torch.int32)
+        self.wr_target, self.wr_prev = z((S, 3), torch.float64), z((S, 3), torch.float64)
+        self.alive, self.run_return = z(S, torch.uint8), z(S, torch.float64)
+        io = abi.AdrpRaceAgentsIO()
+        io.struct_size = ctypes.sizeof(abi.AdrpRaceAgentsIO)
+        io.num_envs, io.num_drones, io.obs_dim, io.num_gates = E, N, D, int(env.cfg.track.num_gates)
+        for k in ("wr_gate", "wr_target", "wr_prev", "alive", "run_return", "run_length"):
+            setattr(io, k, getattr(self, k).data_ptr())
+        self._io, self._ref = io, ctypes.byref(io)
+        # the roster (adrp_race_roster_io)
+        self.clock = z(E, torch.int32)
+        self.phase = z((3, E, N), torch.uint8)                      # took off, notified, landed
+        self.setpoints = torch.zeros((N, E, 4), **f32)              # the frozen policies', drone-major
+        self.learner_act = torch.zeros((self.L, E, 4), **f32)       # the learner's env_act, drone-major
+        self.codes = z((E, N), torch.int32)
+        self.args = z((E, N, abi.CMD_ARGS), torch.float64)
+        self.commander = None
+        rio = abi.AdrpRaceRosterIO()
+        rio.struct_size = ctypes.sizeof(abi.AdrpRaceRosterIO)
+        rio.num_envs, rio.num_drones, rio.num_learners, rio.ctrl_freq = E, N, self.L, float(env.CTRL_FREQ)
+        for n, r in enumerate(self.roles):
+            rio.role[n] = r
+            rio.learner_index[n] = self.learners.index(n) if r == abi.ROSTER_LEARNER else -1
+        for k in ("clock", "phase", "setpoints", "learner_act", "codes", "args"):
+            setattr(rio, k, getattr(self, k).data_ptr())
+        self._rio, self._rref = rio, ctypes.byref(rio)
+        self.lib = _lib.load()
+        self.rollouts = 0
+
+    @property
+    def has_hardcoded(self):
+        return abi.ROSTER_HARDCODED in self.roles
+
+    def set_opponent(self, n, policy):
+        """replace the frozen policy of drone ``n`` (a roster entry that was given as a ``DevicePolicy``), e.g. by a
+        newer ``PPOLearner.snapshot()``; takes effect from the next step.  The caller closes the old one."""
+        from .policy import MODES
+        if self.roles[n] != abi.ROSTER_POLICY:
+            raise ValueError(f"drone {n} is not a frozen-policy drone of this roster")
+        if policy.mode == MODES["raw"] or policy.act_dim != 4 or policy.in_dim > self.env.h.D or policy.device != self.env.device:
+            raise ValueError(f"drone {n}: a race policy emits a setpoint (mode 'relative' or 'absolute', 4 outputs) from a "
+                             "drone's observation row, on the env's device")
+        self._frozen = [(k, policy if k == n else p) for k, p in self._frozen]
+        self.roster[n] = policy
+
+    def _gather(self, dst, obs):
+        """the learner drones' rows of obs [E, N, D] into the compact dst [L E, D]: one strided copy per learner"""
+        rows = dst.view(self.L, self.num_envs, -1)
+        for l, n in enumerate(self.learners):
+            rows[l].copy_(obs[:, n])
+
+    def _tick(self, mask):
+        self._check(self.lib.adrp_race_roster_tick(self._rref, None if mask is None else mask.data_ptr(), self._stream()),
+                    "adrp_race_roster_tick")
+
+    def reset(self):
+        """resets every env; the scripted drones plan their splines from this observation (the one host-side
+        piece: scipy, or the device planner's status read)"""
+        with torch.cuda.device(self.obs.device):
+            obs, _ = self.env.reset()
+            if self.has_hardcoded:
+                from .hardcoded import HardCodedCommander
+                if self.commander is None:
+                    self.commander = HardCodedCommander(obs, device=self.env.device, planner=self.planner)
+                    ref, off = self.commander.reference_trajectory, self.commander._offset
+                    assert off.dtype == torch.int64 and off.is_contiguous() and ref.is_contiguous()
+                    self._rio.ref_len, self._rio.ref, self._rio.offset = self.commander.L, ref.data_ptr(), off.data_ptr()
+                else:
+                    self.commander.replan(obs)
+            self._agents_reset(obs, None)
+            self._tick(None)
+            self._last_start.fill_(1.0)
+            self._env_obs = obs
+
+    def _collect(self):
+        env, pol, R, E, N, D = self.env, self.policy, self.E, self.num_envs, self.N, self.env.h.D
+        if getattr(self, "_env_obs", None) is None:
+            raise RuntimeError("RosterRolloutCollector.reset() first: the scripted drones plan from the reset observation")
+        lib, base = self.lib, self.rollouts * self.T
+        obs = self._env_obs
+        env_act = self.learner_act.view(R, 4)
+        cmd = (self.codes, self.args)
+        for t in range(self.T):
+            self._gather(self.obs[t], obs)
+            self.episode_starts[t].copy_(self._last_start)
+            pol.sample(self.obs[t], self.seed, base + t, env_act=env_act, action=self.actions[t],
+                       value=self.values[t], log_prob=self.log_probs[t])
+            for n, p in self._frozen:
+                # drone n's rows in place: row e at obs + (e * N + n) * D, so base + n * D with stride N * D
+                self._check(lib.adrp_policy_act(p.h, obs.data_ptr() + 4 * n * D, E, N * D, p.mode,
+                                                self.setpoints[n].data_ptr(), self._stream()), "adrp_policy_act")
+            self._check(lib.adrp_race_roster_act(self._rref, self._stream()), "adrp_race_roster_act")
+            obs, _, term, trunc, _ = env.step(cmd)
+            # the bootstrap values: the critic on the learner drones' post-step rows
+            self._gather(self._post, obs)
+            self._values_of(self._post, self._tv)
+            self._check(lib.adrp_race_roster_step_env(
+                self._rref, self._ref, env.h.h, obs.data_ptr(), term.data_ptr(), trunc.data_ptr(), self._tv.data_ptr(),
+                self.gamma, self.rewards[t].data_ptr(), self.valid[t].data_ptr(), self._last_start.data_ptr(),
+                self.ep_return[t].data_ptr(), self.ep_length[t].data_ptr(), self._stream()), "adrp_race_roster_step_env")
+            torch.bitwise_or(term, trunc, out=self._mask)
+            mask = self._mask.view(torch.uint8)
+            obs, _ = env.reset(mask=mask)
+            self._agents_reset(obs, mask)
+            self._tick(mask)
+        self._env_obs = obs
+        self._gather(self._post, obs)
+        self._values_of(self._post, self.last_values)
+        self.last_dones.copy_(self._last_start)
+        rc = lib.adrp_gae(self.rewards.data_ptr(), self.values.data_ptr(), self.episode_starts.data_ptr(),
+                          self.last_values.data_ptr(), self.last_dones.data_ptr(), self.T, R, self.gamma,
+                          self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(), self._stream())
+        self._check(rc, "adrp_gae")
+        self.rollouts += 1
+        return self

@@ -197,6 +197,19 @@ class AdrpRaceAgentsIO(ctypes.Structure):
                 ("wr_gate", _p), ("wr_target", _p), ("wr_prev", _p), ("alive", _p), ("run_return", _p), ("run_length", _p)]
 
 
+ROSTER_NONE, ROSTER_HARDCODED, ROSTER_POLICY, ROSTER_LEARNER = 0, 1, 2, 3   # ADRP_ROSTER_* (the first three: RACE_CTRL_*)
+
+
+class AdrpRaceRosterIO(ctypes.Structure):
+    """adrp_race_roster_io (include/adrp.h): the roster and the caller-owned device buffers of the roster collector"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("num_learners", _i32),
+                ("ref_len", _i32), ("reserved", _i32), ("ctrl_freq", _d),
+                ("role", _arr(_i32, MAX_DRONES)), ("learner_index", _arr(_i32, MAX_DRONES)),
+                ("clock", _p), ("phase", _p), ("ref", _p), ("offset", _p), ("setpoints", _p), ("learner_act", _p),
+                ("codes", _p), ("args", _p)]
+
+
 PLAN_KNOTS, PLAN_COEF, PLAN_OBS_MIN = 20, 16, 28       # ADRP_PLAN_*
 PLAN_NOT_IER0, PLAN_CEILING = 1, 2                     # adrp_race_plan status bits 0 / 1; n in bits 8..15, iterations 16..23
 

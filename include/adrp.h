@@ -669,6 +669,75 @@ int adrp_race_agents_step_env(const adrp_race_agents_io* io, adrp_t* h, const fl
                               uint8_t* valid, float* next_start, double* ep_return, int32_t* ep_length, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Race rosters for per-drone PPO rollouts (rollout.RosterRolloutCollector): some drones of every env are samples
+ * of the policy being trained (LEARNER), the others race them as the scripted HardCodedController (HARDCODED), a
+ * frozen policy (POLICY) or not at all (NONE).  Three small launches per env.step, one lane per slot, 256-lane
+ * blocks, no LDS, no atomics.  csrc/roster_kernel.h.  Handle-less: the caller owns every buffer (all on one
+ * device), every pointer is fixed per step.  L = num_learners; learner l is drone d(l), the drone n with
+ * learner_index[n] = l; learner column c = l * E + e (drone-major, as setpoints).
+ *
+ * adrp_race_roster_act: before env.step.  adrp_race_controllers' launch with the episode time taken per env,
+ * ep_time = (double)clock[e] / ctrl_freq (an IEEE float64 division), and one more role: LEARNER is POLICY's
+ * transform (FULLSTATE, args[0:3] = x, y, z, args[9] = yaw, args[13] = ep_time) of learner_act[learner_index[n]][e],
+ * the env_act adrp_policy_sample wrote for the L * E compact rows.  NONE, HARDCODED and POLICY are
+ * adrp_race_controllers' kinds, bit for bit (one device function serves both kernels).  Every slot of codes and
+ * args is written on every call; phase is updated for HARDCODED drones; clock is only read.
+ *
+ * adrp_race_roster_tick: after the caller's masked env.reset.  For an env with mask[e] != 0 (mask uint8 [E];
+ * NULL: every env) clock[e] = 0 and the three phase flags of its N slots are cleared; for every other env
+ * clock[e] += 1.  One lane per slot, the n = 0 lane owns the clock.
+ *
+ * adrp_race_roster_step: adrp_race_agents_step for the learner drones alone, one lane per learner column c.  It
+ * reads and updates the agent state (agents: the [E*N] arrays of adrp_race_agents_io as they are, so
+ * adrp_race_agents_reset serves unchanged), the obs row, gate and flags of slot j = e * N + d(l), reads term /
+ * trunc of env e and boot_value[c] (float32 [L*E]: the critic on the compact post-step rows), and writes rewards,
+ * valid, next_start, ep_return, ep_length at c of [L*E] outputs: what adrp_race_agents_step writes at j, bit for
+ * bit (one device function serves both kernels).  The state of the other slots is not touched.
+ * adrp_race_roster_step_env reads gate / flags from handle h's own device image in place.
+ *
+ * Errors are reported through adrp_last_error(NULL).  Refused with ADRP_ERR_INVALID before any device call: a
+ * NULL io, a struct_size mismatch, num_envs < 1, num_drones outside 1..ADRP_MAX_DRONES, num_learners outside
+ * 1..num_drones, a role outside the four, a learner_index that is not a bijection of the LEARNER drones onto
+ * 0..L-1 or is >= 0 on another role, ctrl_freq <= 0 (act, tick), a NULL clock / phase / codes / args (act, tick),
+ * HARDCODED without ref / offset / ref_len >= 1, POLICY without setpoints, LEARNER without learner_act (act);
+ * for the step what adrp_race_agents_step refuses, an agents io whose num_envs / num_drones differ from the
+ * roster's, a NULL or non-race handle, a handle whose E, N, D differ from the io's.
+ * --------------------------------------------------------------------------------------- */
+#define ADRP_ROSTER_NONE 0          /* = ADRP_RACE_CTRL_NONE */
+#define ADRP_ROSTER_HARDCODED 1     /* = ADRP_RACE_CTRL_HARDCODED */
+#define ADRP_ROSTER_POLICY 2        /* = ADRP_RACE_CTRL_POLICY: a frozen policy's setpoints */
+#define ADRP_ROSTER_LEARNER 3       /* the policy being trained */
+typedef struct adrp_race_roster_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_roster_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  num_learners;    /* L in 1..N */
+    int32_t  ref_len;         /* samples per reference trajectory (HARDCODED) */
+    int32_t  reserved;
+    double   ctrl_freq;       /* env.steps per second of episode time, > 0 */
+    int32_t  role[ADRP_MAX_DRONES];            /* ADRP_ROSTER_* of drone n < N */
+    int32_t  learner_index[ADRP_MAX_DRONES];   /* l of a LEARNER drone, -1 otherwise */
+    int32_t* clock;           /* [E] env.steps since the env's reset */
+    uint8_t* phase;           /* [3][E*N] took off, notified, landed (adrp_race_ctrl_io.phase) */
+    const double*  ref;       /* [E][N][ref_len][3] or NULL without a HARDCODED drone */
+    const int64_t* offset;    /* [E][N], likewise */
+    const float* setpoints;   /* [N][E][4] or NULL without a POLICY drone, 16-byte aligned */
+    const float* learner_act; /* [L][E][4], 16-byte aligned */
+    int32_t* codes;           /* [E][N] out */
+    double*  args;            /* [E][N][ADRP_CMD_ARGS] out, 16-byte aligned */
+} adrp_race_roster_io;
+int adrp_race_roster_act(const adrp_race_roster_io* io, void* stream);
+int adrp_race_roster_tick(const adrp_race_roster_io* io, const uint8_t* mask, void* stream);
+int adrp_race_roster_step(const adrp_race_roster_io* io, const adrp_race_agents_io* agents, const float* obs,
+                          const int32_t* gate, const int32_t* flags, const uint8_t* term, const uint8_t* trunc,
+                          const float* boot_value, double gamma, float* rewards, uint8_t* valid, float* next_start,
+                          double* ep_return, int32_t* ep_length, void* stream);
+int adrp_race_roster_step_env(const adrp_race_roster_io* io, const adrp_race_agents_io* agents, adrp_t* h, const float* obs,
+                              const uint8_t* term, const uint8_t* trunc, const float* boot_value, double gamma,
+                              float* rewards, uint8_t* valid, float* next_start, double* ep_return, int32_t* ep_length,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Device spline planner of the scripted racer (user_controller/HardCodedController.py:63-115: 16 waypoints
  * from the drone's start and the nominal gates, scipy splprep(s = 0.1), splev at L parameter values): what
  * hardcoded.plan computes per drone on the host, for every (env, drone) of a wave in one launch.
