@@ -587,6 +587,31 @@ __device__ __forceinline__ void pin_all(AngK& k) {
     for (int i = 0; i < 10; ++i) pin(k.p[i]);
     pin(k.tan8); pin(k.pi4); pin(k.pi2); pin(k.pi); pin(k.lim); pin(k.lo); pin(k.hi);
 }
+// ---- the hover chain wave's tilt test from the quaternion ------------------------------------
+// HoverAviary truncates at |roll| > 0.4 || |pitch| > 0.4.  In getEulerFromQuaternion's arguments (euler_args:
+// pitch = asin(sarg), roll = atan2(y0, x0)), in real arithmetic,
+//   |pitch| > 0.4  <=>  |sarg| > sin 0.4
+//   |roll|  > 0.4  <=>  |y0| > tan 0.4 x0        for x0 > 0
+// The float64 angles carry a relative error of a few 1e-16, so a lane whose left side is further than
+// kTruncBand (relative) from its threshold gets from these forms the decision fabs(angle) > 0.4 gives on the
+// computed angle.  A lane inside a band, with x0 <= 0, at gimbal lock (|sarg| >= 0.99999: the angles take
+// another branch) or with a NaN is unsure: trunc_from_quat returns false and the caller tests the angles.
+// (A non-finite quaternion component makes sarg non-finite or NaN, which fails |sarg| < 0.99999.)
+// The chain wave holds the constants in SGPR pairs: each is the one scalar operand of its instruction.
+constexpr double kTruncBand = 1e-9;
+struct TruncK {
+    double s_lo, s_hi, t_lo, t_hi;   // sin 0.4 (1 -+ band), tan 0.4 (1 -+ band)
+    double lim;                      // 0.99999
+};
+__device__ __forceinline__ TruncK trunc_consts() {
+    return TruncK{0.3894183423086505 * (1.0 - kTruncBand), 0.3894183423086505 * (1.0 + kTruncBand),
+                  0.4227932187381618 * (1.0 - kTruncBand), 0.4227932187381618 * (1.0 + kTruncBand), 0.99999};
+}
+__device__ __forceinline__ void pin_s(double& x) { asm volatile("" : "+s"(x)); }
+__device__ __forceinline__ void pin_all(TruncK& k) {
+    pin_s(k.s_lo); pin_s(k.s_hi); pin_s(k.t_lo); pin_s(k.t_hi); pin_s(k.lim);
+}
+
 namespace f64 {
 // |x| + |y| is NaN if either is, and within [max, 2 max]
 __device__ __forceinline__ bool atan2_lean_ok(double y, double x, const AngK& k) {

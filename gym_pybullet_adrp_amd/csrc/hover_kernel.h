@@ -522,6 +522,18 @@ __device__ __forceinline__ double euler_yaw_lean(Q4<double> q, const AngK& k) {
     return f64::atan2_lean<false>(a.y2, a.x2, k);
 }
 
+// The chain wave's tilt test without an angle (adrp_device.h, TruncK): false if the lane is unsure, else
+// over = |roll| > 0.4 || |pitch| > 0.4 as the float64 angles of euler_xyz_fast_u decide it
+__device__ __forceinline__ bool trunc_from_quat(Q4<double> q, const TruncK& k, bool& over) {
+    const EulerArgs<double> a = euler_args(q);
+    const double as = fabs_(a.sarg), ay = fabs_(a.y0);
+    const bool p_over = as > k.s_hi, r_over = ay > k.t_hi * a.x0;
+    const bool p_sure = p_over || as < k.s_lo, r_sure = r_over || ay < k.t_lo * a.x0;
+    over = p_over || r_over;
+    return p_sure && r_sure && a.x0 > 0.0 && as < k.lim;
+}
+__device__ __forceinline__ bool trunc_from_quat(Q4<float>, const TruncK&, bool&) { return false; }   // (fp64 kernels only)
+
 // E = 1 persistent step (SPLIT): lane L evaluates Euler angle min(L, 2) of the (duplicated) env with
 // ONE atan2 -- roll (y0, x0), pitch (sarg, sqrt((1 - sarg)(1 + sarg)), the atan2 form of fasin_),
 // yaw (y2, x2) -- and the three come back by readlane: the same arguments as euler_xyz_fast_u
@@ -959,56 +971,99 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DYN = (PH == ADRP_PHYS_DYN);
     static_assert(!HELP || STG, "the reset helper wave pairs with the staged (all lanes live) kernel");
-    __shared__ Real rs_body[HELP ? kResetFields * kStepBlock : 1];
-    __shared__ float rs_obs[HELP ? 12 * kStepBlock : 1];
-    __shared__ float4 rows[STG ? kStepBlock * kRowF4 : 1];
     // ANG: the obs row's angles are computed by the helper waves from the chain's final quaternion (LDS):
     // pitch and yaw by two more waves, the roll by the reset helper, whose own work ends before barrier A.
     // The chain's tail holds none of the three float64 atan2-class evaluations
     constexpr bool ANG = HELP && angle_helpers<Real>();
+    __shared__ Real rs_body[HELP ? kResetFields * kStepBlock : 1];
+    __shared__ float rs_obs[HELP && !ANG ? 12 * kStepBlock : 1];
+    // (ANG: behind the 64 staged rows, the reset obs of the block's envs as three float4 per env, kResetObs)
+    constexpr int kResetObs = kStepBlock * kRowF4;
+    __shared__ float4 rows[STG ? kStepBlock * kRowF4 + (ANG ? 3 * kStepBlock : 0) : 1];
     __shared__ Real ang_q[ANG ? 4 * kStepBlock : 1];
     __shared__ Real ang_r[ANG ? kStepBlock : 1];
     __shared__ Real ang_p[ANG ? kStepBlock : 1];
     __shared__ float ang_y[ANG ? kStepBlock : 1];
     // the block's coalesced copy-out dealt over its waves: float4 columns [cb(w), cb(w + 1)) of the
-    // rows; with the angle helpers the chain wave takes 3 of the 18, the helpers 5 each
+    // rows (the ANG kernels deal the copy-out differently, TROWS below: cb(1) = 0, none for the chain)
     constexpr int kWaves = HELP ? 1 + help_waves<Real>() : 1;
-    constexpr auto cb = [](int w) { return w == 0 ? 0 : (w >= kWaves ? kRowF4 : (kWaves == 2 ? kRowF4 / 2 : 5 * w - 2)); };
-    // TROWS (the ANG kernels): the terminal rows of the done envs leave in two parts.  A done lane of the
-    // chain stores its three kinematic columns from registers (the values it has just staged) and enters
-    // its lane number into done_list at its rank among the done lanes; the count goes to done_cnt.  Behind
-    // barrier B each helper wave copies its five ring columns of those rows from the staged block, twelve
-    // rows per pass over lanes 0..59 (lane l: list entry l / 5, column l % 5): one pass up to twelve done
-    // envs in a block (5.5 at the benched shape), where the chain, one instruction per issue slot, had 15
-    // LDS reads and 15 stores of its own for them.  The ring columns are not touched by a reset, so
-    // they are the terminal row's behind B as before it.
+    constexpr auto cb = [](int w) { return w == 0 ? 0 : (w >= kWaves ? kRowF4 : (kWaves == 2 ? kRowF4 / 2 : 6 * (w - 1))); };
+    // TROWS (the ANG kernels): the chain wave ends at its state stores.  It decides the tilt truncation from
+    // the quaternion (trunc_from_quat), stages its nine kinematic floats that are not angles, writes one byte
+    // per lane (done_b: the env is done), enters the done lanes into done_list at their rank, the count into
+    // done_cnt, takes the reset state of its done lanes from rs_body and stores the state.  The three helper
+    // waves (192 lanes) put their angle into the staged rows as float32 (row float 3, 4, 5) and copy out all
+    // eighteen columns of the block:
+    //   before barrier C, while the chain is still at work, the fifteen ring columns, which are final at
+    //   barrier A: five float4 per lane (helper_ring);
+    //   behind barrier B the three kinematic columns, one float4 per lane (lane g: column g % 3 of row g / 3),
+    //   for a done env from the reset obs (kResetObs) instead of the staged row; and the staged rows of the
+    //   listed envs, which the reset never touches, as terminal rows, ten rows per pass over lanes 0..179
+    //   (lane g: list entry g / 18, column g % 18) (helper_tail).
     constexpr bool TROWS = ANG;
-    constexpr int kSplitCols = 5, kSplitRows = 12;   // ring columns per helper wave, rows per pass
-    static_assert(!TROWS || (cb(2) - cb(1) == kSplitCols && cb(4) - cb(3) == kSplitCols && cb(1) == 3 &&
-                             kSplitCols * kSplitRows <= kStepBlock), "terminal rows: 3 + 3 x 5 columns");
+    constexpr int kHelpLanes = 3 * kStepBlock, kRingF4 = kRowF4 - 3;
+    constexpr int kRingPer = kStepBlock * kRingF4 / kHelpLanes;   // ring float4 per helper lane
+    constexpr int kTermRows = kHelpLanes / kRowF4;                // terminal rows per pass
+    static_assert(!TROWS || (kWaves == 4 && kRingPer * kHelpLanes == kStepBlock * kRingF4 && cb(1) == 0),
+                  "copy-out over three helper waves");
     __shared__ int done_cnt[1];
     __shared__ uint8_t done_list[TROWS ? kStepBlock : 1];
-    // A helper wave's work behind barrier B (tl: its lane, wv: its wave): its five columns of the block's obs
-    // copy-out, and its five ring columns of the done envs' terminal rows.  The count, the first pass's list
-    // entry and, through it, the first pass's float4 are read ahead of the copy-out's stores, needed or not
-    // (a list entry past the count is stale: it is masked to a row of the block and not stored), so that
-    // the common single pass adds one predicated store to the wave's tail and no LDS round trip.
-    [[maybe_unused]] auto helper_tail = [&](int tl, int wv) {
+    __shared__ uint8_t done_b[TROWS ? kStepBlock : 1];
+    // What a helper lane's copies need that depends on the lane alone, formed (and held in registers) while
+    // the wave waits for barrier A.  Byte offsets within `rows`, which are the byte offsets within the block's
+    // obs rows too: ring[j] of ring float4 g + 192 j (column 3 + n % 15 of row n / 15), kin of the lane's
+    // kinematic float4, fix of the same column of the row's reset obs; flag: the row; sub, tcol: the lane's
+    // list entry and column of a terminal row pass
+    struct TailIdx {
+        uint32_t ring[kRingPer], kin, fix, flag, sub, tcol;
+    };
+    [[maybe_unused]] auto tail_index = [&](int tl, int wv) {
+        TailIdx t;
+        const uint32_t g = uint32_t(wv - 1) * kStepBlock + uint32_t(tl);
+#pragma unroll
+        for (int j = 0; j < kRingPer; ++j) {
+            const uint32_t n = g + kHelpLanes * uint32_t(j);
+            const uint32_t row = (n * 4370u) >> 16;   // n / 15 for n < 960
+            t.ring[j] = (row * kRowF4 + 3u + (n - kRingF4 * row)) * 16u;
+            asm volatile("" : "+v"(t.ring[j]));
+        }
+        t.flag = (g * 21846u) >> 16;                  // g / 3 for g < 192
+        t.kin = (t.flag * kRowF4 + (g - 3u * t.flag)) * 16u;
+        t.fix = (kResetObs + g) * 16u;
+        t.sub = (g * 3641u) >> 16;                    // g / 18 for g < 192
+        t.tcol = g - kRowF4 * t.sub;
+        asm volatile("" : "+v"(t.kin), "+v"(t.fix), "+v"(t.flag), "+v"(t.sub), "+v"(t.tcol));
+        return t;
+    };
+    [[maybe_unused]] auto helper_ring = [&](const TailIdx& ti) {
+        const char* lds = reinterpret_cast<const char*>(rows);
+        char* dst = reinterpret_cast<char*>(a.obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
+        float4 o[kRingPer];
+#pragma unroll
+        for (int j = 0; j < kRingPer; ++j) o[j] = *reinterpret_cast<const float4*>(lds + ti.ring[j]);
+#pragma unroll
+        for (int j = 0; j < kRingPer; ++j) store_out(reinterpret_cast<float4*>(dst + ti.ring[j]), o[j]);
+    };
+    // A helper lane's work behind barrier B.  The count, the first pass's list entry and, through it, the first
+    // pass's float4 are read ahead of the obs store, needed or not (a list entry past the count is stale: it
+    // is masked to a row of the block and not stored), so that the common single pass adds one predicated
+    // store to the wave's tail and no LDS round trip.
+    [[maybe_unused]] auto helper_tail = [&](const TailIdx& ti) {
         const int cnt_v = done_cnt[0];
-        const int sub = tl / kSplitCols, c = cb(wv) + tl - kSplitCols * sub;
-        const int row0 = done_list[sub] & (kStepBlock - 1);
-        float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-        float4 o[kSplitCols];
-#pragma unroll
-        for (int j = 0; j < kSplitCols; ++j) o[j] = rows[tl + kStepBlock * (cb(wv) + j)];
-        const float4 t0 = rows[row0 * kRowF4 + c];
-#pragma unroll
-        for (int j = 0; j < kSplitCols; ++j) store_out(dst + tl + kStepBlock * (cb(wv) + j), o[j]);
+        const int row0 = done_list[ti.sub] & (kStepBlock - 1);
+        const uint8_t fl = done_b[ti.flag];
+        const char* lds = reinterpret_cast<const char*>(rows);
+        char* dst = reinterpret_cast<char*>(a.obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
+        const float4 o = *reinterpret_cast<const float4*>(lds + (fl ? ti.fix : ti.kin));
+        float4 t0 = rows[row0 * kRowF4 + int(ti.tcol)];
+        hold(t0.x); hold(t0.y); hold(t0.z); hold(t0.w);   // (the read stays here, ahead of the store)
+        store_out(reinterpret_cast<float4*>(dst + ti.kin), o);
         const int cnt = __builtin_amdgcn_readfirstlane(cnt_v);
-        const bool mine = tl < kSplitCols * kSplitRows;
+        const int sub = int(ti.sub), c = int(ti.tcol);
+        const bool mine = sub < kTermRows;
         float4* tb = reinterpret_cast<float4*>(a.tobs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
         if (mine && sub < cnt) tb[row0 * kRowF4 + c] = t0;
-        for (int base = kSplitRows; base < cnt && base < kStepBlock; base += kSplitRows) {
+        for (int base = kTermRows; base < cnt && base < kStepBlock; base += kTermRows) {
             const int n = base + sub;
             if (mine && n < cnt) {
                 const int row = done_list[n] & (kStepBlock - 1);
@@ -1021,16 +1076,26 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             const int tl = threadIdx.x & (kStepBlock - 1), wv = threadIdx.x / kStepBlock;
             AngK ak = ang_consts();   // the lean angle forms' constants, into VGPRs while the wave is idle
             pin_all(ak);
+            const TailIdx ti = tail_index(tl, wv);
             __syncthreads();   // A: the chain's final quaternion
             const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
             if constexpr (ANG) {   // (this branch is the ANG kernels' alone; fp32 has no lean forms to compile)
-                if (wv == 2) ang_p[tl] = euler_pitch_lean(q, ak);
-                else ang_y[tl] = float(euler_yaw_lean(q, ak));
+                float* rowf = reinterpret_cast<float*>(rows) + tl * (4 * kRowF4);
+                if (wv == 2) {
+                    const double p = euler_pitch_lean(q, ak);
+                    ang_p[tl] = p;
+                    rowf[4] = float(p);
+                } else {
+                    const float y = float(euler_yaw_lean(q, ak));
+                    ang_y[tl] = y;
+                    rowf[5] = y;
+                }
             }
+            if constexpr (TROWS) helper_ring(ti);
             __syncthreads();   // C: pitch and yaw
             __syncthreads();   // B: the final rows
             if constexpr (TROWS) {
-                helper_tail(tl, wv);
+                helper_tail(ti);
                 return;
             }
             float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
@@ -1061,8 +1126,14 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                                           rb.angv.x, rb.angv.y, rb.angv.z};
 #pragma unroll
             for (int k = 0; k < kResetFields; ++k) rs_body[k * kStepBlock + tl] = v[k];
+            if constexpr (ANG) {   // as three float4: the helper waves' copy-out takes them whole (helper_tail)
+                rows[kResetObs + 3 * tl + 0] = make_float4(o[0], o[1], o[2], o[3]);
+                rows[kResetObs + 3 * tl + 1] = make_float4(o[4], o[5], o[6], o[7]);
+                rows[kResetObs + 3 * tl + 2] = make_float4(o[8], o[9], o[10], o[11]);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 12; ++k) rs_obs[k * kStepBlock + tl] = o[k];
+                for (int k = 0; k < 12; ++k) rs_obs[k * kStepBlock + tl] = o[k];
+            }
             // ring part of the obs row, oldest first; the appended action is the newest entry.
             // Every env appends once per env.step and resets keep the ring, so the head is the
             // same for every env in practice: then the slot -> row position map is scalar.
@@ -1090,15 +1161,20 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             reinterpret_cast<float4*>(a.ring)[size_t(head) * E + he] = av;
             [[maybe_unused]] AngK ak = ang_consts();   // (ANG: pinned behind this wave's reset work, before A)
             if constexpr (ANG) pin_all(ak);
+            [[maybe_unused]] TailIdx ti{};
+            if constexpr (TROWS) ti = tail_index(tl, 1);
             __syncthreads();   // A: reset states and ring rows in LDS
             if constexpr (ANG) {   // this wave is idle from here to the copy-out: it takes the roll
                 const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
-                ang_r[tl] = euler_roll_lean(q, ak);
+                const double roll = euler_roll_lean(q, ak);
+                ang_r[tl] = roll;
+                reinterpret_cast<float*>(rows)[tl * (4 * kRowF4) + 3] = float(roll);
+                if constexpr (TROWS) helper_ring(ti);
                 __syncthreads();   // C
             }
-            __syncthreads();   // B: the chain wave's kinematic parts and reset rows
+            __syncthreads();   // B: the chain wave's kinematic parts and done marks
             if constexpr (TROWS) {
-                helper_tail(tl, 1);
+                helper_tail(ti);
                 return;
             }
             // this wave's part of the block's coalesced copy-out
@@ -1282,19 +1358,31 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     a.rew[e] = float(r > Real(0) ? r : Real(0));
     const bool te = d2 < Real(1e-8);   // |target - pos| < 1e-4
     bool tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) || sc >= C.trunc_steps;
+    [[maybe_unused]] bool slow = false;   // ANG: the chain has waited at C for the angles
     if constexpr (ANG) {
         hold(b.w.x); hold(b.w.y); hold(b.w.z);
 #pragma unroll
         for (int k = 0; k < 12; ++k)
             if (k < 3 || k > 5) hold(o12[k]);
-        __syncthreads();   // C: the helpers' roll, pitch and yaw
-        rpy.x = ang_r[threadIdx.x];
-        rpy.y = ang_p[threadIdx.x];
-        o12[3] = float(rpy.x);
-        o12[4] = float(rpy.y);
-        o12[5] = ang_y[threadIdx.x];
+        // The tilt truncation without waiting for an angle (trunc_from_quat).  One unsure lane sends the whole
+        // wave down the path of before: wait at C for the helpers' roll and pitch and test those, so every
+        // input gives the flag it gave.  Either way the wave passes A, C and B once each: on the sure path C
+        // comes behind the state stores, next to B (slow is wave-uniform)
+        TruncK tk = trunc_consts();
+        pin_all(tk);
+        bool over = false;
+        const bool sure = trunc_from_quat(b.q, tk, over);
+        slow = __any(!sure);
+        if (__builtin_expect(slow, 0)) {
+            __syncthreads();   // C: the helpers' roll and pitch
+            rpy.x = ang_r[threadIdx.x];
+            rpy.y = ang_p[threadIdx.x];
+            over = fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
+        }
+        tr = tr || over;
+    } else {
+        tr = tr || fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
     }
-    tr = tr || fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
     a.term[e] = te;
     a.trunc[e] = tr;
     sc += C.S;
@@ -1332,33 +1420,20 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             }
             stage_row<A, B>(my, o12, ring, head1);
         }
-        my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-        my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-        my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-        if constexpr (HELP && !ANG) __syncthreads();   // A: the helper wave's reset states
-        if constexpr (TROWS) {   // (every lane writes the same word)
+        if constexpr (TROWS) {
+            // the chain's end: its nine floats of the row (the helper waves write floats 3, 4, 5), the done marks
+            // for the helper waves' tail, the reset state of its done lanes, the state stores
+            float* mf = reinterpret_cast<float*>(my);
+            mf[0] = o12[0]; mf[1] = o12[1]; mf[2] = o12[2];
+            mf[6] = o12[6]; mf[7] = o12[7];
+            my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
             const unsigned long long done_mask = __ballot(done);
-            done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;
-            if (done && a.tobs) {   // terminal obs: the kinematic columns from here, the ring columns by the helpers
-                float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(e) * D);
-                trow[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-                trow[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-                trow[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+            done_b[threadIdx.x] = done;
+            done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;   // (every lane writes the same word)
+            if (done) {
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi(uint32_t(done_mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(done_mask), 0u));
                 done_list[rank] = uint8_t(threadIdx.x);
-            }
-        }
-        if (done) {
-            if (!TROWS && a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
-                float4 t[kRowF4];
-#pragma unroll
-                for (int k = 0; k < kRowF4; ++k) t[k] = my[k];
-                float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(e) * D);
-#pragma unroll
-                for (int k = 0; k < kRowF4; ++k) trow[k] = t[k];
-            }
-            if constexpr (HELP) {   // BaseAviary.reset from the helper's LDS copy
-                const int t = threadIdx.x;
+                const int t = threadIdx.x;   // BaseAviary.reset from the helper's LDS copy
                 Real v[kResetFields];
 #pragma unroll
                 for (int k = 0; k < kResetFields; ++k) v[k] = rs_body[k * kStepBlock + t];
@@ -1372,25 +1447,60 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                 for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
                 sc = 0;
                 ep += 1;
-#pragma unroll
-                for (int k = 0; k < 12; ++k) o12[k] = rs_obs[k * kStepBlock + t];
-            } else {
-                hover_reset_state(a, C, e, b, sc, ep);
-                hover_obs12(C, b, o12);      // the reset keeps the ring: only the kinematic part changes
             }
+            RACE_SET(t4);
+            store_state();
+            if (!slow) __syncthreads();   // C (the unsure wave passed it above)
+            __syncthreads();              // B: the helper waves copy out
+        } else {
             my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
             my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
             my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-        }
-        RACE_SET(t4);
-        // the state leaves first: its registers are free before the copy-out (holding both
-        // spilled the copy-out buffer to scratch)
-        store_state();
-        __syncthreads();
-        float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-        constexpr int KC = cb(1);   // HELP: the helper waves copy the other columns
+            if constexpr (HELP) __syncthreads();   // A: the helper wave's reset states
+            if (done) {
+                if (a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
+                    float4 t[kRowF4];
 #pragma unroll
-        for (int k = 0; k < KC; ++k) store_out(dst + threadIdx.x + kStepBlock * k, rows[threadIdx.x + kStepBlock * k]);
+                    for (int k = 0; k < kRowF4; ++k) t[k] = my[k];
+                    float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(e) * D);
+#pragma unroll
+                    for (int k = 0; k < kRowF4; ++k) trow[k] = t[k];
+                }
+                if constexpr (HELP) {   // BaseAviary.reset from the helper's LDS copy
+                    const int t = threadIdx.x;
+                    Real v[kResetFields];
+#pragma unroll
+                    for (int k = 0; k < kResetFields; ++k) v[k] = rs_body[k * kStepBlock + t];
+                    b.pos = v3(v[0], v[1], v[2]);
+                    b.q = {v[3], v[4], v[5], v[6]};
+                    b.ql = b.q;
+                    b.vel = v3(v[7], v[8], v[9]);
+                    b.w = v3(v[10], v[11], v[12]);
+                    b.angv = v3(v[13], v[14], v[15]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
+                    sc = 0;
+                    ep += 1;
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) o12[k] = rs_obs[k * kStepBlock + t];
+                } else {
+                    hover_reset_state(a, C, e, b, sc, ep);
+                    hover_obs12(C, b, o12);      // the reset keeps the ring: only the kinematic part changes
+                }
+                my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
+                my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
+                my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+            }
+            RACE_SET(t4);
+            // the state leaves first: its registers are free before the copy-out (holding both
+            // spilled the copy-out buffer to scratch)
+            store_state();
+            __syncthreads();
+            float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+            constexpr int KC = cb(1);   // HELP: the helper wave copies the other columns
+#pragma unroll
+            for (int k = 0; k < KC; ++k) store_out(dst + threadIdx.x + kStepBlock * k, rows[threadIdx.x + kStepBlock * k]);
+        }
     } else {
 #pragma unroll
         for (int p = 0; p < B; ++p) {
