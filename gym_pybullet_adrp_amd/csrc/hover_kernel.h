@@ -127,6 +127,12 @@ constexpr int kResetFields = 16; // pos 3, quat 4, vel 3, w 3, angv 3 of a reset
 #ifndef ADRP_HOVER_ANGLE_HELPERS
 #define ADRP_HOVER_ANGLE_HELPERS 1
 #endif
+// Translation wave (fp64 angle-helper kernels, plain PYB, RPM actions, unrolled sub-steps): the yaw helper,
+// idle before barrier A, runs the translational half of every sub-step from the thrust axes the chain wave
+// hands it through LDS, and the chain wave carries the rotation alone (0: the chain runs both halves)
+#ifndef ADRP_HOVER_TRANS_WAVE
+#define ADRP_HOVER_TRANS_WAVE 1
+#endif
 // (float64 only: in float32 the two extra barriers cost more than the two atan2 they take off the
 // chain, +1.2 % against -1.2 % in float64, A/B round 6)
 template <typename Real>
@@ -224,25 +230,40 @@ __device__ __forceinline__ double clamp100_(double x) { return clamp100_sel(x); 
 // pre-update pose's matrix (what Bullet clamps against).  The result is committed per lane, only where
 // the lane's own |wb| > 100: a slow env never takes the round trip because a wave mate spins fast
 // (batch invariance).  NaN fails the test and passes through, as in btClamp.
-template <typename Real>
+// VEL = false: ω alone (v is not read: the translation wave clamps it, clamp100_vel)
+template <typename Real, bool VEL = true>
 __device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn, V3<Real>& v, const ChainK<Real>& K) {
     const Real c = K.c100;
     const bool fast = wn > c;
     bool big = fast;
-    if constexpr (sizeof(Real) == 8) {   // (fp64 has no med3: the select form of v's clamp goes behind the test too)
+    if constexpr (!VEL) {
+    } else if constexpr (sizeof(Real) == 8) {   // (fp64 has no med3: the select form of v's clamp goes behind the test too)
         const bool bx = fabs_(v.x) > c, by = fabs_(v.y) > c, bz = fabs_(v.z) > c;
         big = fast | bx | by | bz;
     } else {
         v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
     }
     if (__builtin_expect(__any(big), 0)) {
-        if constexpr (sizeof(Real) == 8) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
+        if constexpr (VEL && sizeof(Real) == 8) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
         const M3<Real> R = rot_fm(q);
         const V3<Real> w = mul(R, wb);
         const V3<Real> wc = mulT(R, v3(clamp100_(w.x), clamp100_(w.y), clamp100_(w.z)));
         const Real wnc = hsqrt_nn_(dot(wc, wc), K);
         wb = v3(fast ? wc.x : wb.x, fast ? wc.y : wb.y, fast ? wc.z : wb.z);
         wn = fast ? wnc : wn;
+    }
+}
+// v's half of clamp100_body on a wave of its own.  The clamp is a select per component that leaves a
+// component inside +-100 (and a NaN) as it is, so which wave mates send the wave into it changes no lane's
+// value: voting on v alone here and on ω alone there gives every lane what the common vote gave it.
+template <typename Real>
+__device__ __forceinline__ void clamp100_vel(V3<Real>& v, const ChainK<Real>& K) {
+    if constexpr (sizeof(Real) == 8) {
+        const Real c = K.c100;
+        const bool bx = fabs_(v.x) > c, by = fabs_(v.y) > c, bz = fabs_(v.z) > c;
+        if (__builtin_expect(__any(bx | by | bz), 0)) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
+    } else {
+        v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
     }
 }
 
@@ -263,13 +284,17 @@ __device__ __forceinline__ bool flat_props(const HoverConst<Real>& a) {
 // K: the chain's literal constants (pinned into VGPRs by the fp64 caller, ChainK)
 // EXT: Fext, one more world-frame force through the centre of mass (MultiHoverAviary's downwash), is
 // added to the force sum; without it (HoverAviary) the argument is not read
-template <typename Real, int PH, bool EXT = false>
+// ROT (plain PYB without EXT): the rotational half alone.  Nothing translational feeds the rotation, so b.pos
+// and b.vel are neither read nor written, the plane contact is not tested (returns false) and the caller
+// runs pyb_trans_substep elsewhere, from st.zs of each sub-step and st.zc behind it
+template <typename Real, int PH, bool EXT = false, bool ROT = false>
 __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
                                             const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
                                             const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}, Real* vxy = nullptr) {
     constexpr bool GND = (PH == ADRP_PHYS_PYB_GND || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
+    static_assert(!ROT || (!GND && !DRAG && !EXT), "the rotational half stands alone in plain PYB only");
     // _physics: 4 prop forces + z torque on link 4, LINK_FRAME, cached basis
     const V3<Real> zs = st.zs;
     V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
@@ -326,20 +351,24 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     const V3<Real> rhs = v3(fmx(wb.z, Iw.y, fmx(-wb.y, Iw.z, fmx(-kw, Iw.x, nb.x))),
                             fmx(wb.x, Iw.z, fmx(-wb.z, Iw.x, fmx(-kw, Iw.y, nb.y))),
                             fmx(wb.y, Iw.x, fmx(-wb.x, Iw.y, fmx(-kw, Iw.z, nb.z))));
-    const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(b.vel, b.vel), K);
-    const V3<Real> acc = v3(fmx(-kv, b.vel.x, a.inv_mass * Fw.x), fmx(-kv, b.vel.y, a.inv_mass * Fw.y),
-                            fmx(-kv, b.vel.z, a.inv_mass * Fw.z));
+    V3<Real> acc{};
+    if constexpr (!ROT) {
+        const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(b.vel, b.vel), K);
+        acc = v3(fmx(-kv, b.vel.x, a.inv_mass * Fw.x), fmx(-kv, b.vel.y, a.inv_mass * Fw.y),
+                 fmx(-kv, b.vel.z, a.inv_mass * Fw.z));
+    }
     // ω' = ω + dt R I^-1 rhs in the body frame of the pose the exp map is about to leave: the map
     // rotates about ω' itself, so R'^T ω' = R^T ω' and the body-frame update needs no rotation
     wb = v3(fmx(st.dti.x, rhs.x, wb.x), fmx(st.dti.y, rhs.y, wb.y), fmx(st.dti.z, rhs.z, wb.z));
-    b.vel = v3(b.vel.x + a.dt * acc.x, b.vel.y + a.dt * acc.y, b.vel.z + a.dt * acc.z);
+    if constexpr (!ROT) b.vel = v3(b.vel.x + a.dt * acc.x, b.vel.y + a.dt * acc.y, b.vel.z + a.dt * acc.z);
     Real ang = hsqrt_nn_(dot(wb, wb), K);
-    clamp100_body(b.q, wb, ang, b.vel, K);
+    clamp100_body<Real, !ROT>(b.q, wb, ang, b.vel, K);
     st.wb = wb;
     st.wn = ang;
     // (vxy: nothing in a sub-step reads pos.x / pos.y, so the caller may take this sub-step's horizontal
     // velocity instead and run the same two sums itself afterwards, pyb_chain)
-    if (vxy) {
+    if constexpr (ROT) {
+    } else if (vxy) {
         vxy[0] = b.vel.x; vxy[1] = b.vel.y;
         b.pos.z = fmx(a.dt, b.vel.z, b.pos.z);
     } else {
@@ -386,6 +415,7 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     // lowest point of the body cylinder: cos(tilt) = R22, sin(tilt) = |(R02, R12)|.  It is at
     // least z + zoff - hh - r below the centre, so a wave whose drones are all higher than that
     // skips the exact test (same result)
+    if constexpr (ROT) return false;
     if (__builtin_expect(__any(b.pos.z + a.coll_zoff <= a.coll_hh + a.coll_r + Real(1e-6)), 0)) {
         const Real low = b.pos.z + a.coll_zoff - a.coll_hh * fabs_(st.zc.z) -
                          a.coll_r * hsqrt_nn_(st.zc.x * st.zc.x + st.zc.y * st.zc.y);
@@ -394,6 +424,39 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
             if (b.vel.z < Real(0)) b.vel.z = Real(0);
             return true;
         }
+    }
+    return false;
+}
+
+// The translational half of pyb_substep<ROT = false> in plain PYB without an external force, for a wave that
+// carries pos and vel alone (the hover step's translation wave): the same expressions in the same order, so
+// the same bits.  zs: the sub-step's thrust axis.  The plane contact is the caller's (it needs the pose behind
+// the sub-step): pyb_trans_contact.
+template <typename Real>
+__device__ __forceinline__ void pyb_trans_substep(const HoverConst<Real>& a, V3<Real>& pos, V3<Real>& vel, V3<Real> zs,
+                                                  Real sum_f, const ChainK<Real>& K) {
+    const V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
+    const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(vel, vel), K);
+    const V3<Real> acc = v3(fmx(-kv, vel.x, a.inv_mass * Fw.x), fmx(-kv, vel.y, a.inv_mass * Fw.y),
+                            fmx(-kv, vel.z, a.inv_mass * Fw.z));
+    vel = v3(vel.x + a.dt * acc.x, vel.y + a.dt * acc.y, vel.z + a.dt * acc.z);
+    clamp100_vel(vel, K);
+    pos = v3(fmx(a.dt, vel.x, pos.x), fmx(a.dt, vel.y, pos.y), fmx(a.dt, vel.z, pos.z));
+}
+// pyb_substep's wave-uniform guard of the plane contact test, and the test itself with zc, the third column
+// of the pose behind the sub-step
+template <typename Real>
+__device__ __forceinline__ bool pyb_trans_near_plane(const HoverConst<Real>& a, V3<Real> pos) {
+    return __builtin_expect(__any(pos.z + a.coll_zoff <= a.coll_hh + a.coll_r + Real(1e-6)), 0);
+}
+template <typename Real>
+__device__ __forceinline__ bool pyb_trans_contact(const HoverConst<Real>& a, V3<Real>& pos, V3<Real>& vel, V3<Real> zc) {
+    const Real low = pos.z + a.coll_zoff - a.coll_hh * fabs_(zc.z) -
+                     a.coll_r * hsqrt_nn_(zc.x * zc.x + zc.y * zc.y);
+    if (low < Real(0)) {
+        pos.z -= low;
+        if (vel.z < Real(0)) vel.z = Real(0);
+        return true;
     }
     return false;
 }
@@ -764,13 +827,16 @@ __device__ __forceinline__ BodyOffs<Real> body_offsets(int E, int e, bool lag, b
     return r;
 }
 
+// (kin = false: pos and vel are another wave's to load; they are left zero)
 template <typename Real>
 __device__ __forceinline__ void load_body_at(const Real* f, const BodyOffs<Real>& k, Body<Real>& b, bool lag,
-                                             bool drag, bool dyn) {
-    b.pos = v3(field_at(f, k.o[HF_POS + 0]), field_at(f, k.o[HF_POS + 1]), field_at(f, k.o[HF_POS + 2]));
+                                             bool drag, bool dyn, bool kin = true) {
+    if (kin) b.pos = v3(field_at(f, k.o[HF_POS + 0]), field_at(f, k.o[HF_POS + 1]), field_at(f, k.o[HF_POS + 2]));
+    else b.pos = v3(Real(0), Real(0), Real(0));
     b.q = {field_at(f, k.o[HF_QUAT + 0]), field_at(f, k.o[HF_QUAT + 1]), field_at(f, k.o[HF_QUAT + 2]),
            field_at(f, k.o[HF_QUAT + 3])};
-    b.vel = v3(field_at(f, k.o[HF_VEL + 0]), field_at(f, k.o[HF_VEL + 1]), field_at(f, k.o[HF_VEL + 2]));
+    if (kin) b.vel = v3(field_at(f, k.o[HF_VEL + 0]), field_at(f, k.o[HF_VEL + 1]), field_at(f, k.o[HF_VEL + 2]));
+    else b.vel = v3(Real(0), Real(0), Real(0));
     b.w = v3(field_at(f, k.o[HF_OMEGA + 0]), field_at(f, k.o[HF_OMEGA + 1]), field_at(f, k.o[HF_OMEGA + 2]));
     if (lag) b.ql = {field_at(f, k.o[HF_LINK_QUAT + 0]), field_at(f, k.o[HF_LINK_QUAT + 1]),
                      field_at(f, k.o[HF_LINK_QUAT + 2]), field_at(f, k.o[HF_LINK_QUAT + 3])};
@@ -858,11 +924,20 @@ __device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, cons
 // world frame.  ext(b, st), unless NoExtForce, gives each sub-step one more world-frame force from the
 // state at its start (every lane of the wave calls it: it may exchange across lanes).  Returns true if
 // the plane contact model acted.
+// hand(k, z), unless NoHandOff (plain PYB, no external force, SC > 0): the chain runs the rotational half of
+// every sub-step alone (pyb_substep<ROT>; b.pos and b.vel are not touched, false is returned) and hands the third
+// columns of its poses to whoever runs the translational half: k = 0 that of the cached link basis, k = 1 of
+// the pose at entry, k = s + 2 of the pose behind sub-step s.  Sub-step s takes its thrust axis from k = s with
+// the link lag, from k = s + 1 without, and its contact test from k = s + 2.  The chain only hands out: it
+// never waits for the other side.
 struct NoExtForce {};
-template <typename Real, int PH, int SC, bool DRAG, typename Ext>
+struct NoHandOff {};
+template <typename Real, int PH, int SC, bool DRAG, typename Ext, typename Hand = NoHandOff>
 __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>& b, const Real rpm_in[4], bool lag,
-                                          Ext ext, V3<Real>* wb_out = nullptr, Real* vxy = nullptr) {
+                                          Ext ext, V3<Real>* wb_out = nullptr, Real* vxy = nullptr, Hand hand = Hand{}) {
     constexpr bool EXT = !__is_same(Ext, NoExtForce);
+    constexpr bool HAND = !__is_same(Hand, NoHandOff);
+    static_assert(!HAND || (!EXT && !DRAG && SC > 0 && PH == ADRP_PHYS_PYB), "the hand-off is plain PYB's");
     // (a local copy: nothing the sub-steps store can alias it, so what depends on the RPMs alone is
     // computed once for the unrolled sub-steps)
     const Real rpm[4] = {rpm_in[0], rpm_in[1], rpm_in[2], rpm_in[3]};
@@ -886,6 +961,8 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
     HoverConst<Real> Cp = C;
     if constexpr (sizeof(Real) == 8) {
         pin_all(K);
+        // (HAND: mass, gravity, inv_mass and coll_* are the translational half's alone; leaving their pins out
+        // here measured no gain by the A/B rule, profiles/ab_hover_transwave.txt, so the list stays one)
         pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass); pin(Cp.ang_max);
         pin(Cp.ixx); pin(Cp.iyy); pin(Cp.izz); pin(Cp.inv_ixx); pin(Cp.inv_iyy); pin(Cp.inv_izz);
         pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
@@ -907,12 +984,19 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
     }
     st.wn = hsqrt_nn_(dot(b.w, b.w), K);
     st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
+    if constexpr (HAND) {
+        hand(0, st.zs);
+        hand(1, st.zc);
+    }
     bool touched = false;
     // vxy (SC > 0, no external force): the horizontal position is left at its value before the chain and the
     // SC sub-steps' horizontal velocities come back in vxy[2 s], vxy[2 s + 1]: the caller runs
     // pos.x = fma(dt, vxy[2 s], pos.x), likewise y, in order (pos_xy_sums: the same operations, the same bits)
     auto substep = [&](int s) {
-        if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
+        if constexpr (HAND) {
+            pyb_substep<Real, PH, false, true>(Cp, b, st, rpm, sum_f, P, tau_z, K);
+            hand(s + 2, st.zc);
+        } else if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
         else touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K, V3<Real>{}, vxy ? vxy + 2 * s : nullptr);
 #pragma unroll
         for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
@@ -1009,6 +1093,60 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     __shared__ int done_cnt[1];
     __shared__ uint8_t done_list[TROWS ? kStepBlock : 1];
     __shared__ uint8_t done_b[TROWS ? kStepBlock : 1];
+    // TW: the translation wave.  With plain PYB and no external force the translational half of a sub-step
+    // (force, |v|, velocity and its clamp, position, plane contact) feeds nothing back into the rotation; all
+    // it takes from there is the thrust axis, which with the link lag is the z axis of the pose TWO sub-steps
+    // back.  Wave 3, the yaw helper, otherwise idle before barrier A, runs that half for the chain's lanes:
+    //   the chain (pyb_chain's hand-off) writes the z axis of each of its poses into slot k of tw_zxy / tw_zz
+    //   (k = 0: cached link basis, 1: pose at entry, s + 2: pose behind sub-step s), then tw_mark[k].  It only
+    //   writes: no load of pos / vel, no wait, no poll before A.  One wave's LDS operations complete in order,
+    //   so the mark is visible after the data.  (LDS keeps whatever the last workgroup on the CU left: wave 3
+    //   clears the marks and waits for the clears to land ahead of a bare s_barrier that the helper waves pass
+    //   at their head and the chain wave ahead of its first slot write: the head barrier.)
+    //   wave 3 loads pos, vel and the action itself, forms the prop force sum as pyb_chain does, and per
+    //   sub-step s polls the mark of its thrust axis and runs pyb_trans_substep; only when a lane is near the
+    //   plane does it also wait for slot s + 2 (the pose behind the sub-step) for the contact test.  It owns the
+    //   contact counter, the reward, `terminated`, the position limits of `truncated` (one flag byte per lane,
+    //   tw_flag) and row floats 0-2 and 6-8, and leaves the final pos / vel in tw_out, indexed as rs_body is:
+    //   the chain takes the six values behind A from there or, for a done lane, from rs_body by one select of
+    //   the base.  Every state store stays on the chain.
+    constexpr bool TW = TROWS && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0 && ADRP_HOVER_TRANS_WAVE != 0;
+    constexpr int kSlots = SC + 2, kTwOut = HF_VEL + 3;
+    using Real2 = Real __attribute__((ext_vector_type(2)));
+    __shared__ Real2 tw_zxy[TW ? kSlots * kStepBlock : 1];
+    __shared__ Real tw_zz[TW ? kSlots * kStepBlock : 1];
+    __shared__ int tw_mark[TW ? kSlots : 1];
+    __shared__ Real tw_out[TW ? kTwOut * kStepBlock : 1];
+    __shared__ uint8_t tw_flag[TW ? kStepBlock : 1];
+#ifdef ADRP_RACE_TIMING
+    __shared__ unsigned long long tw_time[1];
+#endif
+    // The marks are relaxed workgroup-scope atomics (plain ds_read / ds_write, no s_waitcnt of their own); the
+    // empty asm keeps the compiler from moving the data accesses across them, the LDS keeps a wave's order.
+    [[maybe_unused]] auto slot_wait = [&](int k) {   // one LDS word per poll; the chain wave is co-resident and always arrives
+        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&tw_mark[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0)
+            __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");
+    };
+    [[maybe_unused]] auto slot_read = [&](int k, int tl) {
+        const Real2 xy = tw_zxy[k * kStepBlock + tl];
+        return v3(Real(xy.x), Real(xy.y), tw_zz[k * kStepBlock + tl]);
+    };
+    [[maybe_unused]] auto slot_write = [&](int k, V3<Real> z) {   // the chain wave's hand-off (stores only)
+        const int tl = threadIdx.x;
+        // The chain's head barrier sits here, ahead of its first LDS write and behind its loads and the pre-loop:
+        // the translation wave's lgkmcnt(0) in front of the barrier also covers that wave's kernel-argument
+        // loads, which come in cold (later than the chain's state loads), and by now they have
+        if (k == 0) __builtin_amdgcn_s_barrier();
+        Real2 xy;
+        xy.x = z.x; xy.y = z.y;
+        tw_zxy[k * kStepBlock + tl] = xy;
+        tw_zz[k * kStepBlock + tl] = z.z;
+        if (k > 0) {   // (slot 0 goes with slot 1)
+            asm volatile("" ::: "memory");
+            __hip_atomic_store(&tw_mark[k], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
     // What a helper lane's copies need that depends on the lane alone, formed (and held in registers) while
     // the wave waits for barrier A.  Byte offsets within `rows`, which are the byte offsets within the block's
     // obs rows too: ring[j] of ring float4 g + 192 j (column 3 + n % 15 of row n / 15), kin of the lane's
@@ -1074,13 +1212,93 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     if constexpr (HELP) {
         if (ANG && threadIdx.x >= 2 * kStepBlock) {   // angle helpers: pitch (wave 2), yaw (wave 3)
             const int tl = threadIdx.x & (kStepBlock - 1), wv = threadIdx.x / kStepBlock;
+            // TW, wave 3: its loads first, the marks cleared (and the clears landed) before the head barrier
+            [[maybe_unused]] const bool trans = TW && __builtin_amdgcn_readfirstlane(wv) == 3;
+            [[maybe_unused]] V3<Real> tp{}, tv{};
+            [[maybe_unused]] float4 tact = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            [[maybe_unused]] float trew = 0.0f;
+            [[maybe_unused]] bool tterm = false;
+            if constexpr (TW) {
+                if (trans) {
+                    const int te_ = int(blockIdx.x) * kStepBlock + tl;
+                    auto fld = [&](int k) {
+                        if constexpr (FO == 1) return field_at(a.f, (uint32_t(k) * uint32_t(a.E) + uint32_t(te_)) * uint32_t(sizeof(Real)));
+                        else return a.f[size_t(k) * a.E + te_];
+                    };
+                    tp = v3(fld(HF_POS + 0), fld(HF_POS + 1), fld(HF_POS + 2));
+                    tv = v3(fld(HF_VEL + 0), fld(HF_VEL + 1), fld(HF_VEL + 2));
+                    tact = reinterpret_cast<const float4*>(a.act)[te_];
+                    if (tl < kSlots) __hip_atomic_store(&tw_mark[tl], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the clears are in LDS
+                }
+                __builtin_amdgcn_s_barrier();   // head: no mark of this launch is written before every clear
+            }
             AngK ak = ang_consts();   // the lean angle forms' constants, into VGPRs while the wave is idle
             pin_all(ak);
             const TailIdx ti = tail_index(tl, wv);
+            if constexpr (TW) {
+                if (trans) {   // the translational half of the eight sub-steps, behind the chain's thrust axes
+                    const bool lag = C.link_lag;
+                    ChainK<Real> K = chain_consts<Real>();
+                    HoverConst<Real> Cp = C;
+                    pin(K.k004); pin(K.c100); pin(K.nn_min);
+                    pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass);
+                    pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
+                    // the prop force sum: pyb_chain's statements (products and sums apart: no contraction)
+                    const float ta[4] = {tact.x, tact.y, tact.z, tact.w};
+                    Real sum_f = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const Real rpm = C.hover_rpm * Real(rpm_gain(ta[i]));
+                        const Real r2 = rpm * rpm;
+                        const Real f = r2 * C.kf;
+                        sum_f += f;
+                    }
+                    bool touched = false;
+#pragma unroll
+                    for (int s = 0; s < SC; ++s) {
+                        const int k = lag ? s : s + 1;
+                        slot_wait(k > 0 ? k : 1);
+                        pyb_trans_substep(Cp, tp, tv, slot_read(k, tl), sum_f, K);
+                        if (pyb_trans_near_plane(Cp, tp)) {   // (rare) the pose behind this sub-step
+                            slot_wait(s + 2);
+                            touched |= pyb_trans_contact(Cp, tp, tv, slot_read(s + 2, tl));
+                        }
+                    }
+                    if (touched && a.contact_count) atomicAdd(a.contact_count, 1);
+                    // reward, terminated and the position limits of truncated (HoverAviary.py:68-117): the chain's
+                    // expressions; the chain adds the step limit and the tilt to the flag byte's second bit
+                    const Real dx = C.target[0] - tp.x, dy = C.target[1] - tp.y, dz = C.target[2] - tp.z;
+                    const Real d2 = dx * dx + dy * dy + dz * dz;
+                    const Real r = Real(2) - d2 * d2;
+                    trew = float(r > Real(0) ? r : Real(0));
+                    tterm = d2 < Real(1e-8);
+                    const bool te = tterm;
+                    const bool trp = fabs_(tp.x) > Real(1.5) || fabs_(tp.y) > Real(1.5) || tp.z > Real(2.0);
+                    tw_out[(HF_POS + 0) * kStepBlock + tl] = tp.x; tw_out[(HF_POS + 1) * kStepBlock + tl] = tp.y;
+                    tw_out[(HF_POS + 2) * kStepBlock + tl] = tp.z;
+                    tw_out[(HF_VEL + 0) * kStepBlock + tl] = tv.x; tw_out[(HF_VEL + 1) * kStepBlock + tl] = tv.y;
+                    tw_out[(HF_VEL + 2) * kStepBlock + tl] = tv.z;
+                    tw_flag[tl] = uint8_t((te ? 1 : 0) | (trp ? 2 : 0));
+#ifdef ADRP_RACE_TIMING
+                    if (tl == 0) tw_time[0] = __builtin_amdgcn_s_memtime();   // this wave's arrival at A
+#endif
+                }
+            }
             __syncthreads();   // A: the chain's final quaternion
             const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
             if constexpr (ANG) {   // (this branch is the ANG kernels' alone; fp32 has no lean forms to compile)
                 float* rowf = reinterpret_cast<float*>(rows) + tl * (4 * kRowF4);
+                if constexpr (TW) {
+                    if (trans) {   // what of the translation the chain does not wait for: behind A, where this wave has slack
+                        const int te_ = int(blockIdx.x) * kStepBlock + tl;
+                        a.rew[te_] = trew;
+                        a.term[te_] = tterm;
+                        rowf[0] = float(tp.x); rowf[1] = float(tp.y); rowf[2] = float(tp.z);
+                        rowf[6] = float(tv.x); rowf[7] = float(tv.y); rowf[8] = float(tv.z);
+                    }
+                }
                 if (wv == 2) {
                     const double p = euler_pitch_lean(q, ak);
                     ang_p[tl] = p;
@@ -1106,6 +1324,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             const int tl = threadIdx.x - kStepBlock;
             const int he = blockIdx.x * kStepBlock + tl;
             const int E = a.E;
+            if constexpr (TW) __builtin_amdgcn_s_barrier();   // head (the translation wave's marks are clear)
             // the action ring: its part of the obs row is independent of the physics, so this
             // wave loads it, stages it in LDS and appends the action (deque.append)
             const float4 av = reinterpret_cast<const float4*>(a.act)[he];
@@ -1204,12 +1423,13 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     Body<Real> b;
     int32_t sc, ep, head_ld;
     if (fit) {
-        load_body_at<Real>(a.f, fo, b, lag, DRAG, DYN);
+        load_body_at<Real>(a.f, fo, b, lag, DRAG, DYN, !TW);
         sc = field_at(a.ist, io[HI_STEP]); ep = field_at(a.ist, io[HI_EPISODE]); head_ld = field_at(a.ist, io[HI_RING_HEAD]);
         field_form_end();
     } else {
         load_body(a, e, b, lag, DRAG, DYN);
         sc = a.ist[HI_STEP * E + e]; ep = a.ist[HI_EPISODE * E + e]; head_ld = a.ist[HI_RING_HEAD * E + e];
+        if constexpr (TW) b.pos = b.vel = v3(Real(0), Real(0), Real(0));   // (the translation wave's: these loads are dead)
     }
     const int32_t head = head_ld;
     float act[A];
@@ -1272,7 +1492,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     bool touched = false;
     V3<Real> wbf = v3(Real(0), Real(0), Real(0));   // ANG: the chain's final ω, still in the body frame
     // ANG with unrolled sub-steps: pos.x / pos.y are summed behind barrier A too (pyb_chain's vxy)
-    constexpr bool LATE_XY = ANG && !DYN && SC > 0;
+    constexpr bool LATE_XY = ANG && !DYN && SC > 0 && !TW;
     Real vxy[LATE_XY ? 2 * SC : 2] = {};
 #ifdef ADRP_RACE_TIMING
     // loads landed: the rpm gains and the state are consumed by the first sub-step
@@ -1286,6 +1506,8 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         } else {
             for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
         }
+    } else if constexpr (TW) {   // the rotational half; the z axes of the poses go to the translation wave
+        pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{}, &wbf, nullptr, slot_write);
     } else {
         touched = pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{}, ANG ? &wbf : nullptr, LATE_XY ? vxy : nullptr);
     }
@@ -1323,7 +1545,23 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         const int tl = threadIdx.x;
         ang_q[tl] = b.q.x; ang_q[kStepBlock + tl] = b.q.y; ang_q[2 * kStepBlock + tl] = b.q.z;
         ang_q[3 * kStepBlock + tl] = b.q.w;
+#ifdef ADRP_RACE_TIMING
+        [[maybe_unused]] const uint64_t t_a = __builtin_amdgcn_s_memtime();   // the chain's arrival at A
+#endif
         __syncthreads();   // A: the quaternion out; the reset helper's states and ring rows in
+#ifdef ADRP_RACE_TIMING
+        if constexpr (TW) {   // [20] / [21]: cycles the translation wave arrived at A before / behind the chain
+            if (threadIdx.x == 0) {
+                const uint64_t t_w = tw_time[0];
+                atomicAdd(&g_race_phase[t_a >= t_w ? 20 : 21], (unsigned long long)(t_a >= t_w ? t_a - t_w : t_w - t_a));
+            }
+        }
+#endif
+        if constexpr (TW) {   // the translation wave's final pos / vel, read while the chain has arithmetic to do
+            const Real* src = tw_out + threadIdx.x;
+            b.pos = v3(src[(HF_POS + 0) * kStepBlock], src[(HF_POS + 1) * kStepBlock], src[(HF_POS + 2) * kStepBlock]);
+            b.vel = v3(src[(HF_VEL + 0) * kStepBlock], src[(HF_VEL + 1) * kStepBlock], src[(HF_VEL + 2) * kStepBlock]);
+        }
         // while the three helper waves take one angle each, the chain does what only it can: ω back to the
         // world frame (deferred by pyb_chain), the conversions, the reward and the angle-free truncation tests
         // (hold: arithmetic carries no order against a barrier, and the compiler had placed most of this
@@ -1331,7 +1569,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         // starts from is taken behind A here, and what it gives is finished before C below)
         hold(b.q.x); hold(b.q.y); hold(b.q.z); hold(b.q.w);
         hold(wbf.x); hold(wbf.y); hold(wbf.z);
-        hold(b.pos.x); hold(b.pos.y); hold(b.pos.z);
+        if constexpr (!TW) { hold(b.pos.x); hold(b.pos.y); hold(b.pos.z); }
         if constexpr (LATE_XY) {   // the horizontal position sums of the sub-steps, deferred to here
 #pragma unroll
             for (int k = 0; k < 2 * SC; ++k) hold(vxy[k]);
@@ -1341,29 +1579,38 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                 b.pos.y = fmx(C.dt, vxy[2 * s + 1], b.pos.y);
             }
         }
-        hold(b.vel.x); hold(b.vel.y); hold(b.vel.z);
+        if constexpr (!TW) { hold(b.vel.x); hold(b.vel.y); hold(b.vel.z); }
         if constexpr (!DYN) b.w = mul(rot_fm(b.q), wbf);
         const V3<Real> w = C.physics == ADRP_PHYS_DYN ? b.angv : b.w;   // hover_obs12's row, the angles below
-        o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z);
-        o12[6] = float(b.vel.x); o12[7] = float(b.vel.y); o12[8] = float(b.vel.z);
+        if constexpr (!TW) {   // (TW: row floats 0-2 and 6-8 are the translation wave's)
+            o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z);
+            o12[6] = float(b.vel.x); o12[7] = float(b.vel.y); o12[8] = float(b.vel.z);
+        }
         o12[9] = float(w.x);     o12[10] = float(w.y);    o12[11] = float(w.z);
     } else if (split) {
         rpy = hover_obs12_split(C, b, o12);
     } else {
         rpy = hover_obs12(C, b, o12);
     }
-    const Real dx = C.target[0] - b.pos.x, dy = C.target[1] - b.pos.y, dz = C.target[2] - b.pos.z;
-    const Real d2 = dx * dx + dy * dy + dz * dz;
-    const Real r = Real(2) - d2 * d2;
-    a.rew[e] = float(r > Real(0) ? r : Real(0));
-    const bool te = d2 < Real(1e-8);   // |target - pos| < 1e-4
-    bool tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) || sc >= C.trunc_steps;
+    bool te, tr;
+    if constexpr (TW) {   // the translation wave's flag byte: terminated, a position limit passed
+        const uint8_t fl = tw_flag[threadIdx.x];
+        te = (fl & 1) != 0;
+        tr = (fl & 2) != 0 || sc >= C.trunc_steps;
+    } else {
+        const Real dx = C.target[0] - b.pos.x, dy = C.target[1] - b.pos.y, dz = C.target[2] - b.pos.z;
+        const Real d2 = dx * dx + dy * dy + dz * dz;
+        const Real r = Real(2) - d2 * d2;
+        a.rew[e] = float(r > Real(0) ? r : Real(0));
+        te = d2 < Real(1e-8);   // |target - pos| < 1e-4
+        tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) || sc >= C.trunc_steps;
+    }
     [[maybe_unused]] bool slow = false;   // ANG: the chain has waited at C for the angles
     if constexpr (ANG) {
         hold(b.w.x); hold(b.w.y); hold(b.w.z);
 #pragma unroll
         for (int k = 0; k < 12; ++k)
-            if (k < 3 || k > 5) hold(o12[k]);
+            if (TW ? k > 8 : (k < 3 || k > 5)) hold(o12[k]);
         // The tilt truncation without waiting for an angle (trunc_from_quat).  One unsure lane sends the whole
         // wave down the path of before: wait at C for the helpers' roll and pitch and test those, so every
         // input gives the flag it gave.  Either way the wave passes A, C and B once each: on the sure path C
@@ -1383,7 +1630,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     } else {
         tr = tr || fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
     }
-    a.term[e] = te;
+    if constexpr (!TW) a.term[e] = te;
     a.trunc[e] = tr;
     sc += C.S;
     const bool done = a.autoreset && (te || tr);
@@ -1424,9 +1671,13 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             // the chain's end: its nine floats of the row (the helper waves write floats 3, 4, 5), the done marks
             // for the helper waves' tail, the reset state of its done lanes, the state stores
             float* mf = reinterpret_cast<float*>(my);
-            mf[0] = o12[0]; mf[1] = o12[1]; mf[2] = o12[2];
-            mf[6] = o12[6]; mf[7] = o12[7];
-            my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+            if constexpr (TW) {
+                mf[9] = o12[9]; mf[10] = o12[10]; mf[11] = o12[11];
+            } else {
+                mf[0] = o12[0]; mf[1] = o12[1]; mf[2] = o12[2];
+                mf[6] = o12[6]; mf[7] = o12[7];
+                my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+            }
             const unsigned long long done_mask = __ballot(done);
             done_b[threadIdx.x] = done;
             done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;   // (every lane writes the same word)

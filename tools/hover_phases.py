@@ -52,5 +52,8 @@ for E in SIZES:
     print(json.dumps({"E": E, "kernel": env.kernel_name, "kernel_us": float(np.mean(ms)) * 1e3,
                       "mean_cycles_per_wave": {p: round(sums[i] / waves) for i, p in enumerate(PHASES)},
                       "max_cycles_per_launch": {p: round(mx[i] / nk) for i, p in enumerate(PHASES)},
-                      "waves_with_reset": sums[9] / waves, "done_lanes_per_step": sums[7] / nk}), flush=True)
+                      "waves_with_reset": sums[9] / waves, "done_lanes_per_step": sums[7] / nk,
+                      # kernels with a translation wave: cycles it reached barrier A before (behind) the chain wave
+                      "trans_wave_ahead_at_A": round(sums[20] / waves), "trans_wave_behind_at_A": round(sums[21] / waves)}),
+          flush=True)
     env.close()
