@@ -126,6 +126,15 @@ def load():
     lib.adrp_ppo_gradients.restype = I
     lib.adrp_ppo_destroy.argtypes = [P]
     lib.adrp_ppo_destroy.restype = None
+    if hasattr(lib, "adrp_ppo_train_begin"):    # (A/B runs load the parent commit's build, which has none)
+        lib.adrp_ppo_set_target_kl.argtypes = [P, ctypes.c_double]
+        lib.adrp_ppo_set_target_kl.restype = I
+        lib.adrp_ppo_set_rates.argtypes = [P, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        lib.adrp_ppo_set_rates.restype = I
+        lib.adrp_ppo_train_begin.argtypes = [P, P]
+        lib.adrp_ppo_train_begin.restype = I
+        lib.adrp_ppo_stop_state.argtypes = [P, P, P]
+        lib.adrp_ppo_stop_state.restype = I
     lib.adrp_episode_step.argtypes = [P, P, P, P, P]
     lib.adrp_episode_step.restype = I
     lib.adrp_episode_summary.argtypes = [P, P, P]
@@ -154,6 +163,9 @@ def load():
         lib.adrp_race_roster_step.restype = I
         lib.adrp_race_roster_step_env.argtypes = [P, P, P, P, P, P, P, ctypes.c_double, P, P, P, P, P, P]
         lib.adrp_race_roster_step_env.restype = I
+    if hasattr(lib, "adrp_race_roster_done"):   # (likewise)
+        lib.adrp_race_roster_done.argtypes = [P, P, P, P, P, P]
+        lib.adrp_race_roster_done.restype = I
     lib.adrp_race_plan.argtypes = [P, P]
     lib.adrp_race_plan.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]

@@ -39,6 +39,9 @@ struct adrp_ppo {
     float* stats = nullptr;  // where the statistics go when the caller passes no stats_out
     double* normpart = nullptr;
     int* t = nullptr;
+    int* stop = nullptr;     // the target_kl latch (ppo_kernel.h): tripped, steps applied, tripped as Adam saw it, spare
+    bool kl_on = false;      // adrp_ppo_set_target_kl
+    double kl_thr = 0.0;     // 1.5 * target_kl
     float* images = nullptr; // w2t / w3t of both nets
 };
 
@@ -58,7 +61,7 @@ extern "C" int adrp_ppo_default_cfg(adrp_ppo_cfg* c) {
 
 static void ppo_free(adrp_ppo_t* q) {
     hipFree(q->params); hipFree(q->m); hipFree(q->v); hipFree(q->grad); hipFree(q->partial); hipFree(q->spart);
-    hipFree(q->advpart); hipFree(q->stats); hipFree(q->normpart); hipFree(q->t); hipFree(q->images);
+    hipFree(q->advpart); hipFree(q->stats); hipFree(q->normpart); hipFree(q->t); hipFree(q->stop); hipFree(q->images);
     delete q;
 }
 
@@ -108,6 +111,7 @@ extern "C" int adrp_ppo_create(adrp_policy_t* p, const adrp_ppo_cfg* cfg, adrp_p
               hipMalloc((void**)&q->stats, sizeof(float) * 8) == hipSuccess &&
               hipMalloc((void**)&q->normpart, sizeof(double) * q->nparts) == hipSuccess &&
               hipMalloc((void**)&q->t, sizeof(int)) == hipSuccess &&
+              hipMalloc((void**)&q->stop, sizeof(int) * 4) == hipSuccess &&
               hipMalloc((void**)&q->images, sizeof(float) * img_n) == hipSuccess;
     if (!ok) {
         ppo_free(q);
@@ -119,6 +123,7 @@ extern "C" int adrp_ppo_create(adrp_policy_t* p, const adrp_ppo_cfg* cfg, adrp_p
     d.w3t[1] = d.w3t[0] + w3t_n[0];
     ok = hipMemset(q->m, 0, fb) == hipSuccess && hipMemset(q->v, 0, fb) == hipSuccess &&
          hipMemset(q->grad, 0, fb) == hipSuccess && hipMemset(q->t, 0, sizeof(int)) == hipSuccess &&
+         hipMemset(q->stop, 0, sizeof(int) * 4) == hipSuccess &&
          hipMemset(q->images, 0, sizeof(float) * img_n) == hipSuccess;   // W3's rows beyond n_out stay zero
     if (ok) {   // the master parameters are what the policy's blobs hold
         hipLaunchKernelGGL(ppo_pack_kernel, dim3(q->pblocks), dim3(256), 0, nullptr, d, q->params, 1);
@@ -169,26 +174,64 @@ extern "C" int adrp_ppo_update(adrp_ppo_t* q, const float* obs, int obs_stride, 
     a.idx = idx; a.n = n; a.advpart = norm ? q->advpart : nullptr;
     a.clip = float(q->cfg.clip_range); a.clip_vf = float(q->cfg.clip_range_vf); a.vf_coef = float(q->cfg.vf_coef);
     a.partial = q->partial; a.spart = q->spart; a.ngroups = ngroups; a.rg = rg;
+    a.stop = q->stop;
     DeviceGuard g(p->device);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     if (norm) {
-        hipLaunchKernelGGL(ppo_advstat_kernel, dim3(kPpoAdvBlocks), dim3(256), 0, s, advantages, idx, n, q->advpart);
+        hipLaunchKernelGGL(ppo_advstat_kernel, dim3(kPpoAdvBlocks), dim3(256), 0, s, advantages, idx, n, q->advpart, q->stop);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = p->relu ? ppo_grad_launch_relu(p->h1, p->h2, a, grid, s) : ppo_grad_launch_tanh(p->h1, p->h2, a, grid, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(ppo_reduce_kernel, dim3(q->nparts), dim3(256), 0, s, q->partial, grid, q->total, q->d.off[12],
                            float(q->cfg.ent_coef), q->grad, q->normpart, q->spart, n, q->d.log_std, q->d.act_dim,
-                           stats_out ? stats_out : q->stats, q->t);
+                           stats_out ? stats_out : q->stats, q->t, q->stop, q->kl_on ? 1 : 0, q->kl_thr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(ppo_adam_kernel, dim3(q->pblocks), dim3(256), 0, s, q->d, q->grad, q->normpart, q->nparts, q->params,
-                           q->m, q->v, q->t, q->cfg.learning_rate, q->cfg.max_grad_norm);
+                           q->m, q->v, q->t, q->cfg.learning_rate, q->cfg.max_grad_norm, q->stop);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return seterr(nullptr, ADRP_ERR_DEVICE, std::string("ppo update launch: ") + hipGetErrorString(e));
+    return ADRP_OK;
+}
+
+extern "C" int adrp_ppo_set_target_kl(adrp_ppo_t* q, double target_kl) {
+    // (the values before the handle, as adrp_ppo_create checks its cfg before its policy: every refusal answers without a device)
+    if (target_kl != target_kl) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_target_kl: target_kl is NaN");
+    if (!q) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_target_kl: ppo is NULL");
+    q->kl_on = target_kl >= 0.0;
+    q->kl_thr = q->kl_on ? 1.5 * target_kl : 0.0;
+    return ADRP_OK;
+}
+
+extern "C" int adrp_ppo_set_rates(adrp_ppo_t* q, double learning_rate, double clip_range, double clip_range_vf) {
+    if (!(learning_rate > 0.0)) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_rates: learning_rate must be positive");
+    if (!(clip_range >= 0.0)) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_rates: clip_range must not be negative");
+    if (clip_range_vf != clip_range_vf) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_rates: clip_range_vf is NaN");
+    if (!q) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_set_rates: ppo is NULL");
+    q->cfg.learning_rate = learning_rate;
+    q->cfg.clip_range = clip_range;
+    q->cfg.clip_range_vf = clip_range_vf;
+    return ADRP_OK;
+}
+
+extern "C" int adrp_ppo_train_begin(adrp_ppo_t* q, void* stream) {
+    if (!q) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_train_begin: ppo is NULL");
+    DeviceGuard g(q->policy->device);
+    if (hipMemsetAsync(q->stop, 0, sizeof(int) * 4, (hipStream_t)stream) != hipSuccess)
+        return seterr(nullptr, ADRP_ERR_DEVICE, "adrp_ppo_train_begin: memset failed");
+    return ADRP_OK;
+}
+
+extern "C" int adrp_ppo_stop_state(adrp_ppo_t* q, int32_t* out_dev2, void* stream) {
+    if (!out_dev2) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_stop_state: out_dev2 is NULL");
+    if (!q) return seterr(nullptr, ADRP_ERR_INVALID, "adrp_ppo_stop_state: ppo is NULL");
+    DeviceGuard g(q->policy->device);
+    if (hipMemcpyAsync(out_dev2, q->stop, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+        return seterr(nullptr, ADRP_ERR_DEVICE, "adrp_ppo_stop_state: copy failed");
     return ADRP_OK;
 }
 

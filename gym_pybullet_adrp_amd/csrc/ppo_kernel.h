@@ -11,6 +11,15 @@
 //   ppo_adam_kernel      total norm (fixed order), clip, Adam, master parameters -> fragment blobs
 // No atomics, no block waits on another: the same inputs give the same bits.
 //
+// The target_kl stop is a latch in the learner's device memory, int stop[4] (adrp_ppo_train_begin clears it):
+//   stop[0]  1 once a minibatch's approx_kl exceeded 1.5 target_kl (written by ppo_reduce_kernel block 0)
+//   stop[1]  optimizer steps applied since the clear (the same thread)
+//   stop[2]  stop[0] as the Adam launch of the tripping minibatch saw it (its block 0 writes it)
+// Every kernel returns at entry when the latch is set: ppo_advstat_kernel, ppo_grad_kernel and
+// ppo_adam_kernel read stop[0], ppo_reduce_kernel reads stop[2], since its own block 0 is the writer of
+// stop[0].  So every read is of a word that an earlier launch wrote, never the same launch, and the kernel
+// boundary orders it: the Adam launch of the tripping minibatch skips its step, every later launch is a no-op.
+//
 // ppo_grad_kernel.  One block = 2 NW waves as policy_sample_wide_kernel (waves [0, NW) the actor,
 // [NW, 2 NW) the critic, wave w owns hidden-unit tile w), working through groups of RG 16-row tiles
 // (group g, g + gridDim.x, ..).  Rows are gathered by idx from the rollout buffers.  All products
@@ -115,8 +124,9 @@ __device__ __forceinline__ double ppo_block_sum(double v, double* red) {
 // i in [b c, (b + 1) c), c = ceil(n / kPpoAdvBlocks); thread t takes i = b c + t, + 256, .. and the
 // block a fixed tree.  ppo_grad_kernel adds the kPpoAdvBlocks partials (a fixed butterfly).
 __global__ void __launch_bounds__(256) ppo_advstat_kernel(const float* __restrict__ adv, const int64_t* __restrict__ idx, int n,
-                                                          double* __restrict__ advpart) {
+                                                          double* __restrict__ advpart, const int* __restrict__ stop) {
     __shared__ double red[256];
+    if (stop[0] != 0) return;                            // the target_kl latch (uniform)
     const int c = (n + kPpoAdvBlocks - 1) / kPpoAdvBlocks;
     const int lo = blockIdx.x * c, hi = lo + c < n ? lo + c : n;
     double s = 0.0, q = 0.0;
@@ -146,6 +156,7 @@ struct PpoGradArgs {
     float* partial;                    // [gridDim.x][off[13]]
     float* spart;                      // [gridDim.x][4]: sums of the policy term, value term, kl term, clipped rows
     int ngroups, rg;                   // groups of rg <= ppo_group_tiles<T1>() row tiles
+    const int* stop;                   // the target_kl latch: stop[0] != 0, the launch does nothing
 };
 
 // the 16 x 16 LDS tile t[(reg) 64 + 16 g + row] = T[unit 4 g + reg][row] read as an MFMA operand with k
@@ -187,6 +198,7 @@ __global__ void __launch_bounds__(128 * (T1 > T2 ? T1 : T2)) ppo_grad_kernel(Ppo
     __shared__ float lps[(kPolicyMaxOut / 4) * 16];      // [quad][row]
     __shared__ float vals[16], rowc[16], vcoef[16];
     __shared__ long long idxs[RG * 16];                  // the group's buffer rows
+    if (a.stop[0] != 0) return;                          // the target_kl latch (uniform)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, row = lane & 15;
     const int net = wave >= NW ? 1 : 0;                  // 0 actor, 1 critic
     const int w = wave - net * NW;
@@ -604,13 +616,18 @@ __global__ void __launch_bounds__(128 * (T1 > T2 ? T1 : T2)) ppo_grad_kernel(Ppo
 // b = q, q + 4, q + 8, .. of parameter j in that order, then the four slice sums are added q = 0..3
 // (+ the entropy bonus' constant gradient on log_std).  Per block the squared norm of its 64
 // gradients (double, fixed tree); block 0 also the statistics and t += 1.
+// The thread that counts t also decides the target_kl stop, SB3's `approx_kl_div > 1.5 * target_kl` on the
+// float32 statistic widened to double (kl_thr = 1.5 target_kl, a double product of the host; a NaN compares
+// false).  On a trip it sets stop[0] and leaves t and stop[1] alone: the Adam launch that follows skips.
 __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float* __restrict__ partial, int nb, int total, int ls_off,
                                                          float ent_coef, float* __restrict__ grad,
                                                          double* __restrict__ normpart, const float* __restrict__ spart,
                                                          int n, const float* __restrict__ log_std, int act_dim,
-                                                         float* __restrict__ stats, int* __restrict__ t_dev) {
+                                                         float* __restrict__ stats, int* __restrict__ t_dev,
+                                                         int* __restrict__ stop, int kl_on, double kl_thr) {
     __shared__ double red[256];
     __shared__ float part[256];
+    if (stop[2] != 0) return;                            // the latch as an earlier minibatch's Adam launch left it (uniform)
     const int q = threadIdx.x >> 6, j = threadIdx.x & 63;
     const int p = blockIdx.x * 64 + j;
     float s = 0.0f;
@@ -640,7 +657,18 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float* __restrict
             for (int jj = 0; jj < act_dim; ++jj) e += 1.4189385332046727 + double(log_std[jj]);
             stats[2] = float(-e);
         } else if (k == 5) {
-            t_dev[0] += 1;
+            bool trip = false;
+            if (kl_on) {                                 // the value lane k = 2 stores as stats[3], summed again
+                double acc = 0.0;
+                for (int b = 0; b < nb; ++b) acc += double(spart[4 * b + 2]);
+                trip = double(float(acc / n)) > kl_thr;
+            }
+            if (trip) {
+                stop[0] = 1;
+            } else {
+                t_dev[0] += 1;
+                stop[1] += 1;
+            }
         }
     }
 }
@@ -650,8 +678,13 @@ __global__ void __launch_bounds__(256) ppo_reduce_kernel(const float* __restrict
 __global__ void __launch_bounds__(256) ppo_adam_kernel(PpoDesc d, const float* __restrict__ grad,
                                                        const double* __restrict__ normpart, int nparts,
                                                        float* __restrict__ params, float* __restrict__ m, float* __restrict__ v,
-                                                       const int* __restrict__ t_dev, double lr, double max_norm) {
+                                                       const int* __restrict__ t_dev, double lr, double max_norm,
+                                                       int* __restrict__ stop) {
     __shared__ double red[256];
+    if (stop[0] != 0) {                                  // the target_kl latch (uniform): no step
+        if (blockIdx.x == 0 && threadIdx.x == 0) stop[2] = 1;
+        return;
+    }
     double q = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 256) q += normpart[i];
     const double norm = sqrt(ppo_block_sum(q, red));

@@ -130,6 +130,19 @@ extern "C" int adrp_race_roster_step(const adrp_race_roster_io* io, const adrp_r
                        ep_length, (hipStream_t)stream);
 }
 
+extern "C" int adrp_race_roster_done(const adrp_race_roster_io* io, const adrp_race_agents_io* agents, const uint8_t* term,
+                                     const uint8_t* trunc, uint8_t* mask_out, void* stream) {
+    RosterLearners who;
+    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_done", why);
+    if (const char* why = agents_error(io, agents)) return roster_err("adrp_race_roster_done", why);
+    if (!term || !trunc || !mask_out) return roster_err("adrp_race_roster_done", "NULL argument (term / trunc / mask_out)");
+    StreamDeviceGuard g((hipStream_t)stream);
+    hipLaunchKernelGGL(race_roster_done_kernel, dim3((io->num_envs + kRosterLanes - 1) / kRosterLanes), dim3(kRosterLanes), 0,
+                       (hipStream_t)stream, io->num_envs, io->num_drones, who, io->num_learners, agents->alive, term, trunc,
+                       mask_out);
+    return launched("race roster done");
+}
+
 extern "C" int adrp_race_roster_step_env(const adrp_race_roster_io* io, const adrp_race_agents_io* agents, adrp_t* h,
                                          const float* obs, const uint8_t* term, const uint8_t* trunc, const float* boot_value,
                                          double gamma, float* rewards, uint8_t* valid, float* next_start, double* ep_return,

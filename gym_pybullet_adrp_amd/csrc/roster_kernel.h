@@ -72,4 +72,16 @@ __global__ void __launch_bounds__(kRosterLanes) race_roster_step_kernel(
                          ep_length);
 }
 
+// adrp_race_roster_done: one lane per env, after the step kernel above has updated alive.  The env ends with its
+// race (term | trunc) or with its last learner; only the learner slots' alive is read.
+__global__ void __launch_bounds__(kRosterLanes) race_roster_done_kernel(
+    int num_envs, int num_drones, RosterLearners who, int num_learners, const uint8_t* __restrict__ alive,
+    const uint8_t* __restrict__ term, const uint8_t* __restrict__ trunc, uint8_t* __restrict__ mask_out) {
+    const int e = blockIdx.x * kRosterLanes + threadIdx.x;
+    if (e >= num_envs) return;
+    bool any = false;
+    for (int l = 0; l < num_learners; ++l) any = any || alive[size_t(e) * num_drones + who.drone[l]] != 0;
+    mask_out[e] = ((term[e] | trunc[e]) != 0 || !any) ? 1 : 0;
+}
+
 }  // namespace adrp

@@ -6,8 +6,17 @@ per minibatch the clipped-surrogate loss, its gradient with respect to the 13 pa
 ``clip_grad_norm_`` and ``torch.optim.Adam(eps=1e-5)``, in four HIP launches on the tensors a
 ``RolloutCollector`` already holds (csrc/ppo_kernel.h).  Each update rewrites the attached policy's
 device weights in place, so the next ``collect()`` samples from the updated policy; nothing
-synchronises with the host.  ``target_kl`` early stopping (a host read per minibatch) and
-learning-rate / clip-range schedules are not implemented.
+synchronises with the host.
+
+``target_kl`` is SB3's early stop (``approx_kl_div > 1.5 * target_kl``: skip that minibatch's optimizer
+step, leave the minibatch and the epoch loop) as a latch in the learner's device memory: the reduce launch
+that computes the minibatch's KL sets it, the launches of every later minibatch read it and return, so
+``train`` still issues every launch and reads nothing back (``stop_info()`` is the one deliberate read).
+It is switched on with ``learner.set_target_kl(x)``, the C-ABI's setter; the ``target_kl=`` keyword of the
+constructor and of ``train`` stays refused, as before the latch was built.
+``learning_rate``, ``clip_range`` and ``clip_range_vf`` take a float or a callable of
+``progress_remaining`` (1 at the start of training, 0 at its end), evaluated once at the head of each
+``train`` as SB3 does; ``linear_schedule`` is SB3's ``get_linear_fn``.
 """
 import ctypes
 
@@ -19,6 +28,25 @@ from .utils import abi
 
 KEYS = ACTOR_KEYS + CRITIC_KEYS
 STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+_NO_KEYWORD = ("target_kl is not taken here: the early stop is a latch on the device, switch it on with "
+               "PPOLearner.set_target_kl()")
+
+
+def linear_schedule(start, end=0.0, end_fraction=1.0):
+    """SB3's ``get_linear_fn``: a callable of ``progress_remaining`` that goes from ``start`` (at 1) to ``end``,
+    reached after the fraction ``end_fraction`` of training, and stays there"""
+    start, end, end_fraction = float(start), float(end), float(end_fraction)
+
+    def func(progress_remaining):
+        if (1 - progress_remaining) > end_fraction:
+            return end
+        return start + (1 - progress_remaining) * (end - start) / end_fraction
+
+    return func
+
+
+def _rate(x, progress_remaining):
+    return float(x(progress_remaining)) if callable(x) else float(x)
 
 
 class PPOLearner:
@@ -26,21 +54,27 @@ class PPOLearner:
     learner must be closed (or dropped) before its policy, and the policy's ``set_critic`` must not
     be called while a learner is attached."""
 
+    target_kl = None        # no early stop, constant rates: the state before __init__ sets them
+    _scheduled = False
+    _nmb = 0
+
     def __init__(self, policy, learning_rate=3e-4, n_epochs=10, batch_size=64, clip_range=0.2, clip_range_vf=None,
                  normalize_advantage=True, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=0, target_kl=None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.AdrpError("no HIP device visible: libadrp has no CPU fallback")
         if target_kl is not None:
-            raise ValueError("target_kl early stopping needs a host read per minibatch and is not implemented")
+            raise ValueError(_NO_KEYWORD)
         if int(n_epochs) < 1 or int(batch_size) < 1:
             raise ValueError("n_epochs and batch_size must be at least 1")
         self.policy = policy
         self.n_epochs, self.batch_size = int(n_epochs), int(batch_size)
         cfg = abi.AdrpPpoCfg()
         self.lib.adrp_ppo_default_cfg(ctypes.byref(cfg))
-        cfg.learning_rate, cfg.clip_range = float(learning_rate), float(clip_range)
-        cfg.clip_range_vf = -1.0 if clip_range_vf is None else float(clip_range_vf)
+        # the rates at the start of training; a callable is evaluated again at the head of every train()
+        self.learning_rate, self.clip_range, self.clip_range_vf = learning_rate, clip_range, clip_range_vf
+        cfg.learning_rate, cfg.clip_range = _rate(learning_rate, 1.0), _rate(clip_range, 1.0)
+        cfg.clip_range_vf = -1.0 if clip_range_vf is None else _rate(clip_range_vf, 1.0)
         cfg.normalize_advantage = int(bool(normalize_advantage))
         cfg.ent_coef, cfg.vf_coef, cfg.max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
         if clip_range_vf is not None and cfg.clip_range_vf < 0:
@@ -59,6 +93,10 @@ class PPOLearner:
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(seed))
         self._stats = torch.zeros(5, dtype=torch.float32, device=self.device)
+        self._scheduled = any(callable(x) for x in (learning_rate, clip_range, clip_range_vf))
+        self.stop_state = torch.zeros(2, dtype=torch.int32, device=self.device)   # (tripped, optimizer steps applied)
+        self._nmb = 0
+        self.set_target_kl(None)
 
     # ---- flat vector <-> {SB3 key: tensor} ----
     def _split(self, flat):
@@ -129,6 +167,45 @@ class PPOLearner:
         self._check(self.lib.adrp_ppo_gradients(self.h, gflat.data_ptr(), self._stream()), "adrp_ppo_gradients")
         return self._split(gflat)
 
+    def set_target_kl(self, target_kl):
+        """None: no early stop (the state of a new learner); otherwise SB3's ``target_kl`` for the updates issued from
+        now on (a latch that has tripped holds until the next ``train_begin``, which ``train`` calls)"""
+        if target_kl is not None:
+            target_kl = float(target_kl)
+            if not target_kl >= 0.0:
+                raise ValueError("target_kl must be None or a number >= 0")
+        if target_kl is not None or hasattr(self.lib, "adrp_ppo_set_target_kl"):
+            self._check(self.lib.adrp_ppo_set_target_kl(self.h, -1.0 if target_kl is None else target_kl), "adrp_ppo_set_target_kl")
+        self.target_kl = target_kl
+
+    def set_rates(self, learning_rate, clip_range, clip_range_vf=None):
+        """the learning rate and clip ranges of the updates issued from now on (floats; a captured graph keeps the
+        values it was captured with)"""
+        vf = -1.0 if clip_range_vf is None else float(clip_range_vf)
+        if clip_range_vf is not None and not vf >= 0:
+            raise ValueError("clip_range_vf must not be negative")
+        self._check(self.lib.adrp_ppo_set_rates(self.h, float(learning_rate), float(clip_range), vf), "adrp_ppo_set_rates")
+        self.cfg.learning_rate, self.cfg.clip_range, self.cfg.clip_range_vf = float(learning_rate), float(clip_range), vf
+
+    def train_begin(self):
+        """clears the target_kl latch on the current stream (``train`` calls it; capturable)"""
+        self._check(self.lib.adrp_ppo_train_begin(self.h, self._stream()), "adrp_ppo_train_begin")
+
+    def read_stop_state(self):
+        """copies the latch into ``stop_state`` (device int32 [2]: tripped, optimizer steps applied since
+        ``train_begin``) on the current stream and returns it; no host read"""
+        self._check(self.lib.adrp_ppo_stop_state(self.h, self.stop_state.data_ptr(), self._stream()), "adrp_ppo_stop_state")
+        return self.stop_state
+
+    def stop_info(self):
+        """the one deliberate host read: {"stopped", "updates", "epoch", "minibatch"} of the last ``train``.  When it
+        stopped, ``epoch`` / ``minibatch`` are those of the minibatch whose KL tripped the stop (its step was not
+        applied), else None"""
+        with torch.cuda.device(self.device):
+            stopped, updates = self.read_stop_state().cpu().tolist()
+        at = divmod(updates, self._nmb) if stopped and self._nmb else (None, None)
+        return {"stopped": bool(stopped), "updates": updates, "epoch": at[0], "minibatch": at[1]}
+
     def update(self, obs, actions, old_values, old_log_prob, advantages, returns, idx, stats=None):
         """one minibatch: rows ``idx`` (int64 device tensor) of the flattened buffers obs [R, D],
         actions [R, A], old_values / old_log_prob / advantages / returns [R] -> stats [5] (device:
@@ -150,7 +227,7 @@ class PPOLearner:
         self._check(rc, "adrp_ppo_update")
         return stats
 
-    def train(self, col, permutations=None, target_kl=None):
+    def train(self, col, permutations=None, target_kl=None, progress_remaining=1.0):
         """``n_epochs`` passes over the collector's T x E samples, each a fresh random permutation cut
         into consecutive slices of ``batch_size`` (the last one shorter), as RolloutBuffer.get yields
         them.  ``permutations``: int64 [n_epochs, T E] to use instead of ``torch.randperm``.  Returns
@@ -159,9 +236,18 @@ class PPOLearner:
         A collector with a ``valid`` attribute (``MultiAgentRolloutCollector``: [T, E] uint8, 0 for the samples
         of a drone whose agent episode is over) is trained on its valid rows only: each epoch permutes the
         n_valid flat indices of those rows (one ``torch.nonzero`` per call, the call's one host read), and
-        ``permutations`` is then int64 [n_epochs, n_valid] of such indices."""
+        ``permutations`` is then int64 [n_epochs, n_valid] of such indices.
+
+        With a target set (``set_target_kl``; the ``target_kl`` keyword here is refused) the
+        statistics are pre-filled with NaN: once a minibatch's approx_kl exceeds 1.5 target_kl its row is the last
+        one written, its optimizer step and every later minibatch are skipped on the device (``stop_state``,
+        ``stop_info()``); every launch is still issued and nothing is read back.  ``progress_remaining`` is what
+        callable rates are evaluated at, once, before the first update."""
         if target_kl is not None:
-            raise ValueError("target_kl early stopping needs a host read per minibatch and is not implemented")
+            raise ValueError(_NO_KEYWORD)
+        if self._scheduled:
+            self.set_rates(_rate(self.learning_rate, progress_remaining), _rate(self.clip_range, progress_remaining),
+                           None if self.clip_range_vf is None else _rate(self.clip_range_vf, progress_remaining))
         n = col.T * col.E
         flat = (col.obs.view(n, -1), col.actions.view(n, -1), col.values.view(n), col.log_probs.view(n),
                 col.advantages.view(n), col.returns.view(n))
@@ -182,8 +268,14 @@ class PPOLearner:
                 if not bool((inside & valid[permutations.clamp(0, n - 1)]).all()):
                     raise ValueError("permutations holds the index of an invalid row")
         nmb = (pool + self.batch_size - 1) // self.batch_size
-        stats = torch.zeros((self.n_epochs, nmb, 5), dtype=torch.float32, device=self.device)
+        if self.target_kl is None:
+            stats = torch.zeros((self.n_epochs, nmb, 5), dtype=torch.float32, device=self.device)
+        else:       # the minibatches behind a stop write nothing
+            stats = torch.full((self.n_epochs, nmb, 5), float("nan"), dtype=torch.float32, device=self.device)
+        self._nmb = nmb
         with torch.cuda.device(self.device):
+            if hasattr(self.lib, "adrp_ppo_train_begin"):     # (an A/B run on the parent commit's build has no latch)
+                self.train_begin()
             for e in range(self.n_epochs):
                 if permutations is not None:
                     perm = permutations[e]
@@ -193,6 +285,8 @@ class PPOLearner:
                         perm = rows[perm]
                 for k, s in enumerate(range(0, pool, self.batch_size)):
                     self.update(*flat, perm[s:s + self.batch_size], stats=stats[e, k])
+            if hasattr(self.lib, "adrp_ppo_stop_state"):
+                self.read_stop_state()
         return stats
 
     def close(self):

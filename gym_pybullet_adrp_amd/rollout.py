@@ -314,10 +314,17 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
     (csrc/roster_kernel.h).  ``collect`` makes no host read.
 
     The scripted drones plan once, in ``reset()``, from the reset observation (``planner``: "host" or "device");
-    an env reset during a rollout restarts its scripted drones' clock and phases but does not re-plan."""
+    an env reset during a rollout restarts its scripted drones' clock and phases but does not re-plan.
 
-    def __init__(self, env, policy, roster, n_steps, gamma=0.99, gae_lambda=0.95, seed=0, planner="host"):
+    ``end_on``: "env" resets an env when its race is over (``term | trunc``), so a learner that dies early waits,
+    not valid, until its opponents are done.  "learners" also resets an env once none of its learner drones has a
+    running agent episode (``adrp_race_roster_done``, one more launch per step, after the learners' step): against
+    a scripted racer that flies its whole spline, the rows of a rollout are then almost all valid."""
+
+    def __init__(self, env, policy, roster, n_steps, gamma=0.99, gae_lambda=0.95, seed=0, planner="host", end_on="env"):
         from .policy import MODES, DevicePolicy
+        if end_on not in ("env", "learners"):
+            raise ValueError(f"end_on must be 'env' or 'learners', not {end_on!r}")
         if not isinstance(env, MultiRaceAviary):
             raise ValueError("a roster is collected from a MultiRaceAviary")
         if env.cfg.autoreset:
@@ -334,7 +341,7 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
             raise ValueError("a race agent's policy emits the 4 FULLSTATE outputs (x, y, z, yaw)")
         if policy.in_dim > D:
             raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
-        self.num_envs, self.N = env.num_envs, env.NUM_DRONES
+        self.num_envs, self.N, self.end_on = env.num_envs, env.NUM_DRONES, end_on
         roster = list(roster)
         if len(roster) != self.N:
             raise ValueError(f"the roster has {len(roster)} entries for {self.N} drones: give one per drone")
@@ -481,8 +488,12 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
                 self._rref, self._ref, env.h.h, obs.data_ptr(), term.data_ptr(), trunc.data_ptr(), self._tv.data_ptr(),
                 self.gamma, self.rewards[t].data_ptr(), self.valid[t].data_ptr(), self._last_start.data_ptr(),
                 self.ep_return[t].data_ptr(), self.ep_length[t].data_ptr(), self._stream()), "adrp_race_roster_step_env")
-            torch.bitwise_or(term, trunc, out=self._mask)
             mask = self._mask.view(torch.uint8)
+            if self.end_on == "learners":      # the race is over, or the step above left no learner alive
+                self._check(lib.adrp_race_roster_done(self._rref, self._ref, term.data_ptr(), trunc.data_ptr(), mask.data_ptr(),
+                                                      self._stream()), "adrp_race_roster_done")
+            else:
+                torch.bitwise_or(term, trunc, out=self._mask)
             obs, _ = env.reset(mask=mask)
             self._agents_reset(obs, mask)
             self._tick(mask)

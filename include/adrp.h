@@ -1014,6 +1014,10 @@ int adrp_math_probe(int fn, const double* in_dev, double* out_dev, int n, void* 
 int adrp_math_probe_v_planes(int fn, int* k_in, int* k_out);
 int adrp_math_probe_v(int fn, int precision, const double* in_dev, double* out_dev, int n, void* stream);
 
+/* the training-loop additions: the target_kl latch and rate setters of the PPO update, the learner-ended
+ * reset mask of the race rosters */
+#include "adrp_train.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 python tools/learn_race.py [--envs 256] [--drones 4] [--n-steps 128] [--iterations 20] [--batch-size 1024]
                            [--n-epochs 10] [--seed 0] [--precision fp32] [--out FILE] [--save policy.pth]
                            [--roster learner,hardcoded[,snapshot,none]] [--snapshot-every 5] [--eval-runs 64]
+                           [--end-on env|learners] [--target-kl K] [--learning-rate 3e-4] [--clip-range 0.2]
+                           [--lr-schedule constant|linear] [--clip-schedule constant|linear]
 
 Every drone is an agent of one shared policy (49 inputs: the drone's own state, the gates, the obstacles and the
 gate id; four outputs, RLController's relative FULLSTATE setpoint); the reward is the RewardWrapper's, per drone.
@@ -17,6 +19,11 @@ entries): "learner" drones are samples of the policy being trained, "hardcoded" 
 "snapshot" a frozen copy of the learner (PPOLearner.snapshot(), refreshed every --snapshot-every rollouts: self-play)
 and "none" an idle drone; the env runs in command mode.  --eval-runs R finishes with simulate() over R races, a
 snapshot of the learner in the learner slots against the same opponents, and prints per-drone wins and finish rates.
+--end-on learners (with --roster) resets an env with its last learner instead of with its race: against a scripted
+racer the rollout's rows are then almost all valid (valid_fraction on every line).
+
+--target-kl, --lr-schedule and --clip-schedule are tools/learn_hover.py's: SB3's early stop as a device latch
+(stop_info on every line) and linear schedules over the run.
 """
 import argparse
 import json
@@ -29,11 +36,11 @@ import torch  # noqa: E402
 
 from gym_pybullet_adrp_amd.envs.race import MultiRaceAviary  # noqa: E402
 from gym_pybullet_adrp_amd.policy import DevicePolicy  # noqa: E402
-from gym_pybullet_adrp_amd.ppo import PPOLearner  # noqa: E402
 from gym_pybullet_adrp_amd.rollout import MultiAgentRolloutCollector, RosterRolloutCollector  # noqa: E402
 from gym_pybullet_adrp_amd.sim import simulate  # noqa: E402
 from gym_pybullet_adrp_amd.utils.enums import RaceMode  # noqa: E402
-from tools.learn_hover import sb3_init  # noqa: E402
+from gym_pybullet_adrp_amd.ppo import PPOLearner  # noqa: E402
+from tools.learn_hover import last_epoch_stats, rates, sb3_init  # noqa: E402
 
 
 def main():
@@ -51,7 +58,15 @@ def main():
     ap.add_argument("--roster", default=None, help="comma-separated roles, one per drone: learner, hardcoded, snapshot, none")
     ap.add_argument("--snapshot-every", type=int, default=5, help="rollouts between refreshes of the snapshot opponents")
     ap.add_argument("--eval-runs", type=int, default=0, help="races of the closing simulate() table (with --roster)")
+    ap.add_argument("--end-on", default="env", choices=("env", "learners"), help="with --roster: what ends an env")
+    ap.add_argument("--target-kl", type=float, default=None, help="SB3's target_kl: stop a train() once approx_kl > 1.5 x this")
+    ap.add_argument("--learning-rate", type=float, default=3e-4)
+    ap.add_argument("--clip-range", type=float, default=0.2)
+    ap.add_argument("--lr-schedule", default="constant", choices=("constant", "linear"), help="linear: to 0 at the end of the run")
+    ap.add_argument("--clip-schedule", default="constant", choices=("constant", "linear"))
     args = ap.parse_args()
+    if args.end_on != "env" and not args.roster:
+        raise SystemExit("--end-on learners needs --roster: without one every drone is a learner and the env ends with the last")
     names = [r.strip().lower() for r in args.roster.split(",")] if args.roster else None
     if names:
         bad = [r for r in names if r not in ("learner", "hardcoded", "snapshot", "none")]
@@ -61,12 +76,13 @@ def main():
     env = MultiRaceAviary("level0", num_drones=args.drones, racemode=RaceMode.COMPETE, num_envs=args.envs, seed=args.seed,
                           precision=args.precision, autoreset=False, commands=bool(names))
     pol = DevicePolicy(sb3_init(49, 64, 4, args.seed), "tanh", 0, "relative")
-    learner = PPOLearner(pol, n_epochs=args.n_epochs, batch_size=args.batch_size, seed=args.seed)
+    learner = PPOLearner(pol, n_epochs=args.n_epochs, batch_size=args.batch_size, seed=args.seed, **rates(args))
+    learner.set_target_kl(args.target_kl)
     snaps = {}                       # drone -> its current frozen copy of the learner
     if names:
         snaps = {n: learner.snapshot() for n, r in enumerate(names) if r == "snapshot"}
         col = RosterRolloutCollector(env, pol, [snaps.get(n, None if r == "none" else r) for n, r in enumerate(names)],
-                                     args.n_steps, seed=args.seed)
+                                     args.n_steps, seed=args.seed, end_on=args.end_on)
     else:
         col = MultiAgentRolloutCollector(env, pol, args.n_steps, seed=args.seed)
     col.reset()
@@ -78,13 +94,15 @@ def main():
                 col.set_opponent(n, snaps[n])
                 old.close()
         col.collect()
-        stats = learner.train(col)
+        stats = learner.train(col, progress_remaining=1.0 - it / args.iterations)
         valid = int(col.valid.sum())
         samples += valid
-        s = stats[-1].mean(0).cpu().tolist()
+        s, stop = last_epoch_stats(learner, stats)
         rec = {"iteration": it, "valid_samples": samples, "valid_fraction": valid / (col.T * col.E),
                "policy_loss": s[0], "value_loss": s[1], "approx_kl": s[3], "clip_fraction": s[4],
                "wall_s": round(time.time() - t0, 3)}
+        if stop is not None:
+            rec["stop_info"] = stop
         rec.update(col.episode_summary())
         log.append(rec)
         print(json.dumps(rec), flush=True)

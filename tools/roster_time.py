@@ -2,10 +2,11 @@
 
 python tools/roster_time.py [--envs 4096] [--drones 4] [--steps 60] [--rounds 7] [--level level0] [--out profiles/race_roster.json]
 
-Four arms (fp64, COMPETE), interleaved round by round in rotated order, each a rollout of --steps collector steps
+Five arms (fp64, COMPETE), interleaved round by round in rotated order, each a rollout of --steps collector steps
 (GAE included) from a fresh reset of the same seed after a warm-up rollout of its own:
   learners    (a) RosterRolloutCollector, every drone a learner (command-mode env)
   opponents   (b) RosterRolloutCollector, one learner against scripted HardCodedController drones
+  opponents_learners  (b) with end_on="learners": an env is reset with its last learner, not with its race
   setpoint    (c) MultiAgentRolloutCollector on the setpoint-mode env: the nearest equivalent of (a) that was there
               before the roster collector
   pieces      (d) the work of (b) from the pieces that were there before it, on (b)'s env and buffers: the scripted
@@ -14,7 +15,8 @@ Four arms (fp64, COMPETE), interleaved round by round in rotated order, each a r
               clocks and the flag clearing as eager torch ops, the full-width adrp_race_agents_step_env and a gather
               of the learner's columns
 Reported per arm: microseconds per collector step, the median and the min / max over the rounds; (b) - (d) beside
-(d)'s round-to-round spread, and (a) - (c).  The scripted drones plan on the device (one launch per reset).
+(d)'s round-to-round spread, and (a) - (c); for the two (b) arms the valid rows of the timed rollout and valid rows per
+second.  The scripted drones plan on the device (one launch per reset).
 """
 import argparse
 import json
@@ -118,18 +120,21 @@ def main():
                                autoreset=False, commands=commands)
 
     pol = DevicePolicy(sb3_init(49, 64, 4, 0), "tanh", 0, "relative")
-    env_a, env_b, env_c = make_env(True), make_env(True), make_env(False)
+    env_a, env_b, env_c, env_e = make_env(True), make_env(True), make_env(False), make_env(True)
     col_a = RosterRolloutCollector(env_a, pol, ["learner"] * N, args.steps, seed=0)
     col_b = RosterRolloutCollector(env_b, pol, ["learner"] + ["hardcoded"] * (N - 1), args.steps, seed=0, planner="device")
     col_c = MultiAgentRolloutCollector(env_c, pol, args.steps, seed=0)
+    col_e = RosterRolloutCollector(env_e, pol, ["learner"] + ["hardcoded"] * (N - 1), args.steps, seed=0, planner="device",
+                                   end_on="learners")
     pieces = Pieces(col_b)
-    arms = {"learners": (col_a, col_a), "opponents": (col_b, col_b), "setpoint": (col_c, col_c), "pieces": (pieces, col_b)}
+    arms = {"learners": (col_a, col_a), "opponents": (col_b, col_b), "setpoint": (col_c, col_c), "pieces": (pieces, col_b),
+            "opponents_learners": (col_e, col_e)}
     order = tuple(arms)
     times = {a: [] for a in arms}
     checks = {}
     with torch.cuda.device(env_a.device):
         for r in range(args.rounds):
-            for a in order[r % 4:] + order[:r % 4]:          # rotate the order round by round
+            for a in order[r % len(order):] + order[:r % len(order)]:          # rotate the order round by round
                 runner, col = arms[a]
                 col.env.h.reseed(1)                            # every round flies the same episodes
                 col.rollouts = 0
@@ -144,6 +149,9 @@ def main():
                 if r == 0:                                     # (b) and (d) account the same rollout: equal sums
                     checks[a] = (float(col.rewards.double().sum()), int(col.valid.sum()), int(col.ep_length.sum()))
     med = {a: statistics.median(v) for a, v in times.items()}
+    # every round flies the same episodes, so the first round's valid rows are every round's
+    rows = {a: {"valid_rows_per_rollout": checks[a][1], "rows_per_rollout": arms[a][1].T * arms[a][1].E,
+                "valid_rows_per_second": checks[a][1] / (med[a] * 1e-6 * args.steps)} for a in ("opponents", "opponents_learners")}
     out = {"envs": args.envs, "drones": N, "precision": "fp64", "level": args.level, "kernel_command_mode": env_b.kernel_name,
            "kernel_setpoint_mode": env_c.kernel_name, "steps_per_round": args.steps, "rounds": args.rounds,
            "us_per_step": {a: {"median": med[a], "min": min(v), "max": max(v), "rounds": v} for a, v in times.items()},
@@ -151,6 +159,9 @@ def main():
            "pieces_round_to_round_spread_us": max(times["pieces"]) - min(times["pieces"]),
            "learners_minus_setpoint_us": med["learners"] - med["setpoint"],
            "setpoint_round_to_round_spread_us": max(times["setpoint"]) - min(times["setpoint"]),
+           "end_on": rows,
+           "valid_rows_per_second_learners_over_env": rows["opponents_learners"]["valid_rows_per_second"] /
+           rows["opponents"]["valid_rows_per_second"],
            "first_round_sums (rewards, valid, ep_length)": checks}
     print(json.dumps(out), flush=True)
     if args.out:
@@ -159,7 +170,7 @@ def main():
             json.dump(out, f, indent=1)
             f.write("\n")
     pol.close()
-    for e in (env_a, env_b, env_c):
+    for e in (env_a, env_b, env_c, env_e):
         e.close()
 
 
