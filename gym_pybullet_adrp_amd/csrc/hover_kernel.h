@@ -133,6 +133,12 @@ constexpr int kResetFields = 16; // pos 3, quat 4, vel 3, w 3, angv 3 of a reset
 #ifndef ADRP_HOVER_TRANS_WAVE
 #define ADRP_HOVER_TRANS_WAVE 1
 #endif
+// Pose hand-off (translation-wave kernels): the chain hands its pose quaternions, which it holds anyway, to
+// the translation wave, which forms their z axes for itself; the chain no longer does (0: the chain hands out
+// z axes)
+#ifndef ADRP_HOVER_POSE_HANDOFF
+#define ADRP_HOVER_POSE_HANDOFF 1
+#endif
 // (float64 only: in float32 the two extra barriers cost more than the two atan2 they take off the
 // chain, +1.2 % against -1.2 % in float64, A/B round 6)
 template <typename Real>
@@ -287,7 +293,9 @@ __device__ __forceinline__ bool flat_props(const HoverConst<Real>& a) {
 // ROT (plain PYB without EXT): the rotational half alone.  Nothing translational feeds the rotation, so b.pos
 // and b.vel are neither read nor written, the plane contact is not tested (returns false) and the caller
 // runs pyb_trans_substep elsewhere, from st.zs of each sub-step and st.zc behind it
-template <typename Real, int PH, bool EXT = false, bool ROT = false>
+// POSE (with ROT): st.zs and st.zc are not formed either (nothing in the rotational half reads them: m3 comes
+// from the increment); whoever runs the translational half forms them from the quaternions, b.q behind each call
+template <typename Real, int PH, bool EXT = false, bool ROT = false, bool POSE = false>
 __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
                                             const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
                                             const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}, Real* vxy = nullptr) {
@@ -295,6 +303,7 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
     constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
     static_assert(!ROT || (!GND && !DRAG && !EXT), "the rotational half stands alone in plain PYB only");
+    static_assert(!POSE || ROT, "the z axes are left out of the rotational half only");
     // _physics: 4 prop forces + z torque on link 4, LINK_FRAME, cached basis
     const V3<Real> zs = st.zs;
     V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
@@ -392,7 +401,7 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     // the basis cached by this step's forwardKinematics is the pre-integration pose
     if (a.link_lag) {
         b.ql = q0;
-        st.zs = st.zc;
+        if constexpr (!POSE) st.zs = st.zc;
         // R'^T col2(R) = third row of the rotation of the increment d = (ax, ch) / |q1|
         const Real s2 = (inv + inv) * inv;
         st.m3 = v3(s2 * (ax.x * ax.z - ch * ax.y), s2 * (ax.y * ax.z + ch * ax.x),
@@ -403,11 +412,11 @@ __device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real
     if constexpr (FULL) {
         st.R = rot_fm(b.q);
         st.zc = col2(st.R);
-    } else {
+    } else if constexpr (!POSE) {
         st.zc = col2_fm(b.q);
     }
     if (!a.link_lag) {
-        st.zs = st.zc;
+        if constexpr (!POSE) st.zs = st.zc;
         st.m3 = v3(Real(0), Real(0), Real(1));
         if constexpr (FULL) st.Rs = st.R;
     }
@@ -930,6 +939,10 @@ __device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, cons
 // the pose at entry, k = s + 2 of the pose behind sub-step s.  Sub-step s takes its thrust axis from k = s with
 // the link lag, from k = s + 1 without, and its contact test from k = s + 2.  The chain only hands out: it
 // never waits for the other side.
+// Pose hand-off (ADRP_HOVER_POSE_HANDOFF): hand(k, q) takes the quaternions themselves, k = s + 2 b.q behind
+// sub-step s, and the receiver forms col2_fm(q): the z axes leave the sub-steps (pyb_substep<POSE>); the pre-loop
+// still forms zs once, for m3.  k = 0 and k = 1 would be b.ql and b.q as loaded: the receiver loads those two
+// itself, and hand(0, .) is called once ahead of the sub-steps with nothing to store.
 struct NoExtForce {};
 struct NoHandOff {};
 template <typename Real, int PH, int SC, bool DRAG, typename Ext, typename Hand = NoHandOff>
@@ -937,6 +950,7 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
                                           Ext ext, V3<Real>* wb_out = nullptr, Real* vxy = nullptr, Hand hand = Hand{}) {
     constexpr bool EXT = !__is_same(Ext, NoExtForce);
     constexpr bool HAND = !__is_same(Hand, NoHandOff);
+    constexpr bool POSE = HAND && ADRP_HOVER_POSE_HANDOFF != 0;
     static_assert(!HAND || (!EXT && !DRAG && SC > 0 && PH == ADRP_PHYS_PYB), "the hand-off is plain PYB's");
     // (a local copy: nothing the sub-steps store can alias it, so what depends on the RPMs alone is
     // computed once for the unrolled sub-steps)
@@ -984,7 +998,9 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
     }
     st.wn = hsqrt_nn_(dot(b.w, b.w), K);
     st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
-    if constexpr (HAND) {
+    if constexpr (POSE) {
+        hand(0, b.q);   // (k = 0, 1 are state fields as loaded, which the receiver loads itself: the call marks the head)
+    } else if constexpr (HAND) {
         hand(0, st.zs);
         hand(1, st.zc);
     }
@@ -993,7 +1009,10 @@ __device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>&
     // SC sub-steps' horizontal velocities come back in vxy[2 s], vxy[2 s + 1]: the caller runs
     // pos.x = fma(dt, vxy[2 s], pos.x), likewise y, in order (pos_xy_sums: the same operations, the same bits)
     auto substep = [&](int s) {
-        if constexpr (HAND) {
+        if constexpr (POSE) {
+            pyb_substep<Real, PH, false, true, true>(Cp, b, st, rpm, sum_f, P, tau_z, K);
+            hand(s + 2, b.q);
+        } else if constexpr (HAND) {
             pyb_substep<Real, PH, false, true>(Cp, b, st, rpm, sum_f, P, tau_z, K);
             hand(s + 2, st.zc);
         } else if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
@@ -1064,7 +1083,10 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     // (ANG: behind the 64 staged rows, the reset obs of the block's envs as three float4 per env, kResetObs)
     constexpr int kResetObs = kStepBlock * kRowF4;
     __shared__ float4 rows[STG ? kStepBlock * kRowF4 + (ANG ? 3 * kStepBlock : 0) : 1];
-    __shared__ Real ang_q[ANG ? 4 * kStepBlock : 1];
+    // (pose hand-off kernels, POSE below: the four quaternion rows live in tw_out's, which nobody else uses)
+    constexpr bool kPoseQ = ANG && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0 && ADRP_HOVER_TRANS_WAVE != 0 &&
+                            ADRP_HOVER_POSE_HANDOFF != 0;
+    __shared__ Real ang_q_own[ANG && !kPoseQ ? 4 * kStepBlock : 1];
     __shared__ Real ang_r[ANG ? kStepBlock : 1];
     __shared__ Real ang_p[ANG ? kStepBlock : 1];
     __shared__ float ang_y[ANG ? kStepBlock : 1];
@@ -1111,12 +1133,28 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     //   the chain takes the six values behind A from there or, for a done lane, from rs_body by one select of
     //   the base.  Every state store stays on the chain.
     constexpr bool TW = TROWS && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0 && ADRP_HOVER_TRANS_WAVE != 0;
+    // Pose hand-off (ADRP_HOVER_POSE_HANDOFF, POSE below): slot k of tw_q takes the pose's quaternion instead, as
+    // two 16-byte halves (the chain holds it anyway, for the next quaternion product), and wave 3 forms the z
+    // axis at each read, thrust axis and contact test alike: col2_fm, the chain's own expression on the chain's
+    // own bits.  tw_zxy / tw_zz are gone.  Slots 0 and 1, the cached link basis and the pose at entry, are state
+    // fields as loaded: wave 3 loads them itself beside pos / vel and needs no mark for them, tw_q holds slots
+    // 2 .. SC + 1 alone, and the final quaternion for the angle helpers goes to the four rows of tw_out that
+    // were unused (ang_q), so that three workgroups still fit the CU's 160 KB as before.  The marks are what they were, one word per slot, never per lane or
+    // per value: a NaN, gimbal-lock or clamped lane is stored and marked like any other.  Nobody waits forever:
+    // wave 3's clear of all kSlots mark words lands before the head barrier and no mark is written ahead of that
+    // barrier; behind it the chain writes every one of its marks without a wait, a poll or a barrier of its own
+    // before A, and wave 3 waits for chain marks alone.  The wait graph is chain -> wave 3, no cycle, and every
+    // polling wave reaches A whatever the data holds.
     constexpr int kSlots = SC + 2, kTwOut = HF_VEL + 3;
+    constexpr bool POSE = TW && ADRP_HOVER_POSE_HANDOFF != 0;
     using Real2 = Real __attribute__((ext_vector_type(2)));
-    __shared__ Real2 tw_zxy[TW ? kSlots * kStepBlock : 1];
-    __shared__ Real tw_zz[TW ? kSlots * kStepBlock : 1];
+    [[maybe_unused]] __shared__ Real2 tw_q[POSE ? 2 * (kSlots - 2) * kStepBlock : 1];
+    __shared__ Real2 tw_zxy[TW && !POSE ? kSlots * kStepBlock : 1];
+    __shared__ Real tw_zz[TW && !POSE ? kSlots * kStepBlock : 1];
     __shared__ int tw_mark[TW ? kSlots : 1];
     __shared__ Real tw_out[TW ? kTwOut * kStepBlock : 1];
+    static_assert(kPoseQ == POSE, "ang_q's home");
+    [[maybe_unused]] Real* const ang_q = POSE ? tw_out + HF_QUAT * kStepBlock : ang_q_own;
     __shared__ uint8_t tw_flag[TW ? kStepBlock : 1];
 #ifdef ADRP_RACE_TIMING
     __shared__ unsigned long long tw_time[1];
@@ -1128,20 +1166,33 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             __builtin_amdgcn_s_sleep(1);
         asm volatile("" ::: "memory");
     };
-    [[maybe_unused]] auto slot_read = [&](int k, int tl) {
-        const Real2 xy = tw_zxy[k * kStepBlock + tl];
-        return v3(Real(xy.x), Real(xy.y), tw_zz[k * kStepBlock + tl]);
+    [[maybe_unused]] auto slot_read = [&](int k, int tl) {   // the z axis of the pose in slot k
+        if constexpr (POSE) {
+            const Real2 xy = tw_q[(2 * k - 4) * kStepBlock + tl], zw = tw_q[(2 * k - 3) * kStepBlock + tl];
+            return col2_fm(Q4<Real>{Real(xy.x), Real(xy.y), Real(zw.x), Real(zw.y)});
+        } else {
+            const Real2 xy = tw_zxy[k * kStepBlock + tl];
+            return v3(Real(xy.x), Real(xy.y), tw_zz[k * kStepBlock + tl]);
+        }
     };
-    [[maybe_unused]] auto slot_write = [&](int k, V3<Real> z) {   // the chain wave's hand-off (stores only)
+    [[maybe_unused]] auto slot_write = [&](int k, auto z) {   // the chain wave's hand-off (stores only): z axis or pose
         const int tl = threadIdx.x;
         // The chain's head barrier sits here, ahead of its first LDS write and behind its loads and the pre-loop:
         // the translation wave's lgkmcnt(0) in front of the barrier also covers that wave's kernel-argument
         // loads, which come in cold (later than the chain's state loads), and by now they have
         if (k == 0) __builtin_amdgcn_s_barrier();
-        Real2 xy;
-        xy.x = z.x; xy.y = z.y;
-        tw_zxy[k * kStepBlock + tl] = xy;
-        tw_zz[k * kStepBlock + tl] = z.z;
+        if constexpr (__is_same(decltype(z), Q4<Real>)) {
+            if (k < 2) return;   // (the cached link basis and the pose at entry: wave 3 loads them as the chain does)
+            Real2 xy, zw;
+            xy.x = z.x; xy.y = z.y; zw.x = z.z; zw.y = z.w;
+            tw_q[(2 * k - 4) * kStepBlock + tl] = xy;
+            tw_q[(2 * k - 3) * kStepBlock + tl] = zw;
+        } else {
+            Real2 xy;
+            xy.x = z.x; xy.y = z.y;
+            tw_zxy[k * kStepBlock + tl] = xy;
+            tw_zz[k * kStepBlock + tl] = z.z;
+        }
         if (k > 0) {   // (slot 0 goes with slot 1)
             asm volatile("" ::: "memory");
             __hip_atomic_store(&tw_mark[k], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1215,6 +1266,7 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
             // TW, wave 3: its loads first, the marks cleared (and the clears landed) before the head barrier
             [[maybe_unused]] const bool trans = TW && __builtin_amdgcn_readfirstlane(wv) == 3;
             [[maybe_unused]] V3<Real> tp{}, tv{};
+            [[maybe_unused]] Q4<Real> tq{}, tql{};
             [[maybe_unused]] float4 tact = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             [[maybe_unused]] float trew = 0.0f;
             [[maybe_unused]] bool tterm = false;
@@ -1227,6 +1279,12 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                     };
                     tp = v3(fld(HF_POS + 0), fld(HF_POS + 1), fld(HF_POS + 2));
                     tv = v3(fld(HF_VEL + 0), fld(HF_VEL + 1), fld(HF_VEL + 2));
+                    if constexpr (POSE) {   // slots 0 and 1 of the hand-off: what the chain loads as b.ql and b.q
+                        tq = {fld(HF_QUAT + 0), fld(HF_QUAT + 1), fld(HF_QUAT + 2), fld(HF_QUAT + 3)};
+                        tql = tq;
+                        if (C.link_lag)
+                            tql = {fld(HF_LINK_QUAT + 0), fld(HF_LINK_QUAT + 1), fld(HF_LINK_QUAT + 2), fld(HF_LINK_QUAT + 3)};
+                    }
                     tact = reinterpret_cast<const float4*>(a.act)[te_];
                     if (tl < kSlots) __hip_atomic_store(&tw_mark[tl], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     asm volatile("" ::: "memory");
@@ -1256,17 +1314,28 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
                         sum_f += f;
                     }
                     bool touched = false;
+                    [[maybe_unused]] bool near = false;
 #pragma unroll
                     for (int s = 0; s < SC; ++s) {
                         const int k = lag ? s : s + 1;
-                        slot_wait(k > 0 ? k : 1);
-                        pyb_trans_substep(Cp, tp, tv, slot_read(k, tl), sum_f, K);
+                        V3<Real> zs;
+                        if (POSE && k < 2) {
+                            zs = col2_fm(k == 0 ? tql : tq);
+                        } else {
+                            slot_wait(k > 0 ? k : 1);
+                            zs = slot_read(k, tl);
+                        }
+                        pyb_trans_substep(Cp, tp, tv, zs, sum_f, K);
                         if (pyb_trans_near_plane(Cp, tp)) {   // (rare) the pose behind this sub-step
                             slot_wait(s + 2);
                             touched |= pyb_trans_contact(Cp, tp, tv, slot_read(s + 2, tl));
+                            near = true;
                         }
                     }
                     if (touched && a.contact_count) atomicAdd(a.contact_count, 1);
+#ifdef ADRP_RACE_TIMING
+                    if (tl == 0 && near) atomicAdd(&g_race_phase[24], 1ull);   // waves that took the near-plane path
+#endif
                     // reward, terminated and the position limits of truncated (HoverAviary.py:68-117): the chain's
                     // expressions; the chain adds the step limit and the tilt to the flag byte's second bit
                     const Real dx = C.target[0] - tp.x, dy = C.target[1] - tp.y, dz = C.target[2] - tp.z;

@@ -54,6 +54,8 @@ for E in SIZES:
                       "max_cycles_per_launch": {p: round(mx[i] / nk) for i, p in enumerate(PHASES)},
                       "waves_with_reset": sums[9] / waves, "done_lanes_per_step": sums[7] / nk,
                       # kernels with a translation wave: cycles it reached barrier A before (behind) the chain wave
-                      "trans_wave_ahead_at_A": round(sums[20] / waves), "trans_wave_behind_at_A": round(sums[21] / waves)}),
+                      "trans_wave_ahead_at_A": round(sums[20] / waves), "trans_wave_behind_at_A": round(sums[21] / waves),
+                      # share of translation waves per launch whose sub-steps took the near-plane (contact test) path
+                      "waves_near_plane": sums[24] / waves}),
           flush=True)
     env.close()
