@@ -569,7 +569,7 @@ __device__ __forceinline__ void expmap_sinc_cos(double x, double* sinc, double* 
 //               clamp: the argument is never near zero)
 // On such arguments they are f64::atan2 / f64::asin operation for operation, so they give the same bits.
 // The caller sends the WHOLE wave to the full functions behind one vote when any lane's arguments are
-// outside (euler_*_lean in hover_kernel.h): no lane ever takes a lean form out of its domain.
+// outside (euler_*_lean in hover_dynamics.h): no lane ever takes a lean form out of its domain.
 struct AngK {
     double p[10];                    // atan2_t's polynomial, highest degree first
     double tan8, pi4, pi2, pi;       // tan(pi/8), pi/4, pi/2, pi
@@ -682,7 +682,7 @@ __device__ __forceinline__ void clamp100_wv(V3<double>& w, V3<double>& v) {
     }
 }
 
-// (the hover chain carries ω in the body frame: its form of this clamp is clamp100_body, hover_kernel.h)
+// (the hover chain carries ω in the body frame: its form of this clamp is clamp100_body, hover_dynamics.h)
 
 // rotation matrix of a unit quaternion (body->world)
 template <typename Real>

@@ -85,7 +85,7 @@ struct adrp_handle {
 
 constexpr int kBlock = kStepBlock;
 // Most envs of a handle whose hover-family step addresses its [field][E] state by 32-bit byte offsets
-// (hover_kernel.h, body_offsets): all 33 fields of the block, the PID fields included, end below 4 GiB.
+// (hover_dynamics.h, body_offsets): all 33 fields of the block, the PID fields included, end below 4 GiB.
 // fp64: 16,268,815 envs; fp32: 32,537,631.  Above it the launchers pick the 64-bit index form of the same
 // kernel (hover_launch.h); the multi-hover, ctrl and persistent kernels branch on E themselves.
 template <typename Real>

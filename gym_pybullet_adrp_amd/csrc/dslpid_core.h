@@ -1,5 +1,5 @@
 // dslpid_core.h — the one copy of DSLPIDControl's two loops for gfx950, shared by the controller fused
-// into the HoverAviary / VelocityAviary step kernels (dslpid_rpm, hover_kernel.h) and the stand-alone
+// into the HoverAviary / VelocityAviary step kernels (dslpid_rpm, hover_dynamics.h) and the stand-alone
 // batched controller (dslpid_control, dslpid_kernel.h).
 //
 // Reference path (FelixWaiblinger/gym-pybullet-adrp @ 2024-10-08):

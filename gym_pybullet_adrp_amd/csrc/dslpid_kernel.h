@@ -7,7 +7,7 @@
 //   _dslPIDAttitudeControl              control/DSLPIDControl.py:212-259
 //   BaseControl.computeControlFromState control/BaseControl.py:55-95 (state[0:3], [3:7], [10:13])
 //
-// The position and attitude loops are dslpid_core.h's, the one copy that dslpid_rpm (hover_kernel.h), the
+// The position and attitude loops are dslpid_core.h's, the one copy that dslpid_rpm (hover_dynamics.h), the
 // controller fused into the HoverAviary / VelocityAviary step kernels, calls too.  That one has the
 // targets of its action types, the default gains and the CF2X mixer compiled in; here the four targets,
 // the gains, the mixer and control_timestep are runtime values, and pos_e and the yaw error are returned.

@@ -11,27 +11,9 @@
 //   _computeObs                envs/BaseRLAviary.py:284-319
 //   _computeReward / _computeTerminated / _computeTruncated    envs/HoverAviary.py:68-117
 //
-// Closed form used per Bullet sub-step (derivation in DESIGN.md §Kernel):
-//   thrust axis  zs = Rs·ẑ  (Rs = link basis cached at the last forwardKinematics)
-//   F_world      = Σf·zs + [Σg·R·ẑ] + B·f_link4 + m·g
-//   n_body       = P × (Rᵀzs) + τz·(Rᵀzs) + [G × ẑ]          P = Σ f_i p_i, G = Σ g_i p_i
-//   ω̇_b          = I⁻¹(n_b − k(1+|ω_b|) I∘ω_b − ω_b × I ω_b),   a_w = F_w/m − k(1+|v|) v
-//   v, ω += dt(·) (clamped ±100);  x += dt v;  q ← normalize((ω̂ sin, cos) ⊗ q)
-// ω is carried in the BODY frame through the sub-steps (wb = Rᵀω; state, obs and Bullet's API keep
-// the world frame: one rotation in before the loop, one out after it).  The exp map rotates the pose
-// about ω' itself, R' = exp([ω' dt]) R, so R'ᵀω' = Rᵀω' and
-//   wb' = wb + dt I⁻¹(n_b − k(1+|wb|) I∘wb − wb × I wb)          exactly, no rotation either way
-//   q'  = normalize(q ⊗ (s·wb', c))                              s = sin(|wb'|dt/2)/|wb'|, c = cos
-//   R'ᵀ col2(R) = third row of rot(δ), δ = (s·wb', c)/|q₁|       the next sub-step's Rᵀzs (lag on)
-//               = (2(δxδz − δwδy), 2(δyδz + δwδx), 1 − 2(δx² + δy²))
-// so no sub-step multiplies by a rotation matrix.  Per physics mode (template, no runtime branch):
-//   PYB, PYB_DW            third columns only: zs (lagged, thrust), zc (current, contact test)
-//   PYB_GND, .._GND_DRAG_DW  additionally the third row of the current R (prop heights) and zc
-//   PYB_DRAG               whole R and lagged Rs for Rs (Rᵀ drag): carries both matrices
-//   DYN                    its own explicit model (dyn_substep)
-// The ±100 clamp is on WORLD coordinates of ω: none can exceed 100 unless |wb| does, so behind a
-// wave-uniform __any(|wb| > 100): w = R wb, clamp, wb = Rᵀ w, committed per lane only where the
-// lane's own |wb| > 100 (clamp100_body; batch invariance).
+// The dynamics (the closed form of a Bullet sub-step, the sub-step chain, the reset draw, the obs row and
+// the state's field addressing) are hover_dynamics.h's, shared with the multi-hover, ctrl and persistent
+// kernels.  This file is the step kernel: one function per wave role and the dispatcher over them.
 //
 // Latency design (E = 4096 is 64 waves on 256 CUs: the kernel is one wave's critical
 // path): no divides or IEEE sqrt in the sub-step chain (reciprocal constants, 1-ulp
@@ -43,1016 +25,133 @@
 // coalesced block with the helper waves (HELP) taking the ring, the resets and the obs angles.
 #pragma once
 
-#include "adrp_device.h"
-#include "dslpid_core.h"
+#include "hover_dynamics.h"
 
 namespace adrp {
-
-// float-field indices of the HoverAviary state snapshot ([field][E], SoA)
-enum HoverField {
-    HF_POS = 0, HF_QUAT = 3, HF_VEL = 7, HF_OMEGA = 10, HF_LAST_RPM = 13, HF_ANGV = 17,
-    HF_LINK_QUAT = 20, HF_NBASE = 24,
-    // DSLPIDControl state (PID / VEL / ONE_D_PID handles only): last_rpy 3, integral_pos_e 3,
-    // integral_rpy_e 3 (control/DSLPIDControl.py:65-79)
-    HF_PID = 24, HF_NPID = 9
-};
-enum HoverInt { HI_STEP = 0, HI_EPISODE = 1, HI_RING_HEAD = 2, HI_N = 3 };
-
-// Per-config constants.  Device-resident (one block per handle, written at create, warm
-// in L2 across launches), or compiled in as literals for the reference's default drone
-// (cf2x_consts: CF2X / cf2x_IROS.urdf at 240 Hz), where they fold into immediates.
-template <typename Real>
-struct HoverConst {
-    int S, trunc_steps, link_lag, physics;   // truncated once step_counter >= trunc_steps
-    Real dt, mass, inv_mass, gravity;
-    Real ixx, iyy, izz, inv_ixx, inv_iyy, inv_izz;
-    Real kf, km, hover_rpm;
-    Real px[4], py[4], pz[4];                // prop link COM offsets (body)
-    Real gnd_kf, prop_r4, gnd_clip;          // kf*GND_EFF_COEFF, PROP_RADIUS/4, GND_EFF_H_CLIP
-    Real drag[3];
-    Real dyn_arm;                            // L/sqrt(2) (Physics.DYN)
-    Real coll_hh, coll_r, coll_zoff;         // collision cylinder half-height, radius, z offset
-    Real ang_max;                            // ANGULAR_MOTION_THRESHOLD / dt
-    Real target[3];
-    // DSLPIDControl (PID / VEL / ONE_D_PID): GRAVITY = g*m (BaseControl.py:35, the env's own
-    // URDF), 1/(4 KF), CTRL_TIMESTEP and its inverse, SPEED_LIMIT as the float32 NumPy uses
-    Real pid_grav, pid_inv4kf, ctrl_dt, ctrl_hz;
-    float speed_limit;
-};
-
-// HoverAviary defaults: cf2x_IROS.urdf, PYB_FREQ 240, CTRL_FREQ 30, target (0,0,1), 8 s.
-// Derived values are the float64 results of BaseAviary.py:117-128's formulas; the host
-// selects this path only when its computed block is bit-identical (adrp.hip).
-template <typename Real>
-__host__ __device__ constexpr HoverConst<Real> cf2x_consts(int physics) {
-    HoverConst<Real> c{};
-    c.S = 8; c.trunc_steps = 1921; c.link_lag = 1; c.physics = physics;
-    c.dt = Real(0.004166666666666667);
-    c.mass = Real(0.03454); c.inv_mass = Real(28.951939779965258); c.gravity = Real(9.8);
-    c.ixx = Real(1.4e-5); c.iyy = Real(1.4e-5); c.izz = Real(2.17e-5);
-    c.inv_ixx = Real(71428.57142857143); c.inv_iyy = Real(71428.57142857143); c.inv_izz = Real(46082.949308755764);
-    c.kf = Real(3.16e-10); c.km = Real(7.94e-12); c.hover_rpm = Real(16364.421890108686);
-    c.px[0] = Real(0.028); c.px[1] = Real(-0.028); c.px[2] = Real(-0.028); c.px[3] = Real(0.028);
-    c.py[0] = Real(0.028); c.py[1] = Real(0.028); c.py[2] = Real(-0.028); c.py[3] = Real(-0.028);
-    c.pz[0] = Real(0); c.pz[1] = Real(0); c.pz[2] = Real(0); c.pz[3] = Real(0);
-    c.gnd_kf = Real(3.5924744399999996e-09); c.prop_r4 = Real(0.0057837); c.gnd_clip = Real(0.03776371349209501);
-    c.drag[0] = Real(9.1785e-7); c.drag[1] = Real(9.1785e-7); c.drag[2] = Real(10.311e-7);
-    c.dyn_arm = Real(0.028072139213105935);
-    c.coll_hh = Real(0.0125); c.coll_r = Real(0.06); c.coll_zoff = Real(0);
-    c.ang_max = Real(188.49555921538757);
-    c.target[0] = Real(0); c.target[1] = Real(0); c.target[2] = Real(1);
-    c.pid_grav = Real(0.338492); c.pid_inv4kf = Real(791139240.5063292);
-    c.ctrl_dt = Real(0.03333333333333333); c.ctrl_hz = Real(30);
-    c.speed_limit = 0.25f;
-    return c;
-}
-
-// reset distribution (only the auto-reset / reset path reads it)
-template <typename Real>
-struct HoverReset {
-    Real init_xyz[3], init_rpy[3], n_xyz[3], n_rpy[3], n_vel[3], n_om[3];
-};
-
-// kernel argument block: pointers and a few scalars only (it is rewritten for every
-// launch, so it is cold in every cache: keep it to two 64-byte lines)
-constexpr int kStepBlock = 64;   // envs per workgroup: one chain wave (E = 4096 -> 64 CUs)
-constexpr int kResetFields = 16; // pos 3, quat 4, vel 3, w 3, angv 3 of a reset state (HELP)
-// HELP kernels: two more helper waves beside the reset helper compute the obs row's pitch and yaw
-// from the chain's final quaternion, and the reset helper, idle by then, the roll; the chain meanwhile
-// rotates ω back to the world frame, converts the row and computes the reward
-// (ADRP_HOVER_ANGLE_HELPERS=0: the chain computes all three angles, one helper wave)
-#ifndef ADRP_PERSIST_SPLIT   // 0: a step of one env (launched or persistent) computes its three obs angles on one lane
-#define ADRP_PERSIST_SPLIT 1
-#endif
-#ifndef ADRP_HOVER_ANGLE_HELPERS
-#define ADRP_HOVER_ANGLE_HELPERS 1
-#endif
-// Translation wave (fp64 angle-helper kernels, plain PYB, RPM actions, unrolled sub-steps): the yaw helper,
-// idle before barrier A, runs the translational half of every sub-step from the thrust axes the chain wave
-// hands it through LDS, and the chain wave carries the rotation alone (0: the chain runs both halves)
-#ifndef ADRP_HOVER_TRANS_WAVE
-#define ADRP_HOVER_TRANS_WAVE 1
-#endif
-// Pose hand-off (translation-wave kernels): the chain hands its pose quaternions, which it holds anyway, to
-// the translation wave, which forms their z axes for itself; the chain no longer does (0: the chain hands out
-// z axes)
-#ifndef ADRP_HOVER_POSE_HANDOFF
-#define ADRP_HOVER_POSE_HANDOFF 1
-#endif
-// (float64 only: in float32 the two extra barriers cost more than the two atan2 they take off the
-// chain, +1.2 % against -1.2 % in float64, A/B round 6)
-template <typename Real>
-constexpr bool angle_helpers() { return ADRP_HOVER_ANGLE_HELPERS != 0 && sizeof(Real) == 8; }
-template <typename Real>
-constexpr int help_waves() { return angle_helpers<Real>() ? 3 : 1; }   // helper waves of a HELP workgroup
-
-template <typename Real>
-struct HoverArgs {
-    const HoverConst<Real>* c;   // device-resident constants (generic path)
-    const HoverReset<Real>* r;
-    Real* f;           // [HF_NBASE][E]
-    float* ring;       // [B][E][A]  (slot-major, the A floats of one env contiguous)
-    int32_t* ist;      // [HI_N][E]
-    const float* act;  // [E][A]
-    float* obs;        // [E][D]
-    float* rew;
-    uint8_t* term;
-    uint8_t* trunc;
-    float* tobs;       // [E][D] or null
-    const uint8_t* mask;  // reset mask or null
-    int32_t* contact_count;  // device counter of ground-model hits (diagnostics) or null
-    uint64_t seed;
-    int64_t env_offset;
-    int E, B, D, autoreset;
-};
-
-template <typename Real>
-struct Body {
-    V3<Real> pos, vel, w;     // w: world ω (PYB) or body rpy_rates (DYN)
-    Q4<Real> q, ql;           // pose quaternion, cached link basis
-    V3<Real> angv;            // DYN: world ω reported by getBaseVelocity
-    Real prev_rpm[4];
-};
-
-// Explicit fused multiply-adds of the PYB sub-step chain.  The hover TUs contract a*b+c only
-// within one source expression (csrc/Makefile CONTRACT: the same bits in every dispatch variant),
-// so the fusions across the V3 operators that the chain wants are written out here.
-__device__ __forceinline__ float fmx(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fmx(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// rot(q) with its products folded into FMAs (20 operations instead of 24)
-template <typename Real>
-__device__ __forceinline__ M3<Real> rot_fm(Q4<Real> q) {
-    const Real x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
-    const Real xx = q.x * x2, zz = q.z * z2;
-    const Real wx = q.w * x2, wy = q.w * y2, wz = q.w * z2;
-    return {Real(1) - fmx(q.y, y2, zz), fmx(q.x, y2, -wz), fmx(q.x, z2, wy),
-            fmx(q.x, y2, wz), Real(1) - fmx(q.x, x2, zz), fmx(q.y, z2, -wx),
-            fmx(q.x, z2, -wy), fmx(q.y, z2, wx), Real(1) - fmx(q.y, y2, xx)};
-}
-
-// float32 1 + 0.05 a, two roundings as NumPy does it (no FMA contraction)
-__device__ __forceinline__ float rpm_gain(float a) {
-#pragma clang fp contract(off)
-    const float m = 0.05f * a;
-    return 1.0f + m;
-}
-
-// third column (body z axis in world) and third row of rot_fm(q): the same expressions, so the same bits
-template <typename Real>
-__device__ __forceinline__ V3<Real> col2_fm(Q4<Real> q) {
-    const Real x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
-    const Real xx = q.x * x2;
-    const Real wx = q.w * x2, wy = q.w * y2;
-    return {fmx(q.x, z2, wy), fmx(q.y, z2, -wx), Real(1) - fmx(q.y, y2, xx)};
-}
-template <typename Real>
-__device__ __forceinline__ V3<Real> row2_fm(Q4<Real> q) {
-    const Real x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
-    const Real xx = q.x * x2;
-    const Real wx = q.w * x2, wy = q.w * y2;
-    return {fmx(q.x, z2, -wy), fmx(q.y, z2, wx), Real(1) - fmx(q.y, y2, xx)};
-}
-
-// What the PYB sub-step chain carries from one sub-step to the next beside the Body.  ω lives in the
-// body frame inside the loop (header comment: no rotation of ω either way, no rotation matrix).
-template <typename Real>
-struct Chain {
-    V3<Real> wb;      // body-frame angular velocity R^T ω
-    Real wn;          // |wb| (= |ω|: the damping term's and the exp map's norm, one sqrt per sub-step)
-    V3<Real> zs;      // thrust axis: third column of the cached link basis (world)
-    V3<Real> zc;      // third column of the current pose's matrix (world)
-    V3<Real> m3;      // R^T zs
-    V3<Real> dti;     // dt I^-1
-    M3<Real> R, Rs;   // PYB_DRAG only (drag goes world -> body -> cached link basis): rot_fm(q), rot_fm(ql)
-};
-
-__device__ __forceinline__ float clamp100_(float x) { return __builtin_amdgcn_fmed3f(x, -100.0f, 100.0f); }
-__device__ __forceinline__ double clamp100_(double x) { return clamp100_sel(x); }
-
-// btClamp(x, -100, 100) of the six coordinate velocities (clamp100_wv) for the body-frame chain.
-// v as there.  ω's coordinates are WORLD coordinates; none can exceed 100 unless |wb| = |ω| does, so
-// behind a wave-uniform test of the norm: w = R wb, clamp, wb = R^T w, and the norm again, with R the
-// pre-update pose's matrix (what Bullet clamps against).  The result is committed per lane, only where
-// the lane's own |wb| > 100: a slow env never takes the round trip because a wave mate spins fast
-// (batch invariance).  NaN fails the test and passes through, as in btClamp.
-// VEL = false: ω alone (v is not read: the translation wave clamps it, clamp100_vel)
-template <typename Real, bool VEL = true>
-__device__ __forceinline__ void clamp100_body(Q4<Real> q, V3<Real>& wb, Real& wn, V3<Real>& v, const ChainK<Real>& K) {
-    const Real c = K.c100;
-    const bool fast = wn > c;
-    bool big = fast;
-    if constexpr (!VEL) {
-    } else if constexpr (sizeof(Real) == 8) {   // (fp64 has no med3: the select form of v's clamp goes behind the test too)
-        const bool bx = fabs_(v.x) > c, by = fabs_(v.y) > c, bz = fabs_(v.z) > c;
-        big = fast | bx | by | bz;
-    } else {
-        v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
-    }
-    if (__builtin_expect(__any(big), 0)) {
-        if constexpr (VEL && sizeof(Real) == 8) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
-        const M3<Real> R = rot_fm(q);
-        const V3<Real> w = mul(R, wb);
-        const V3<Real> wc = mulT(R, v3(clamp100_(w.x), clamp100_(w.y), clamp100_(w.z)));
-        const Real wnc = hsqrt_nn_(dot(wc, wc), K);
-        wb = v3(fast ? wc.x : wb.x, fast ? wc.y : wb.y, fast ? wc.z : wb.z);
-        wn = fast ? wnc : wn;
-    }
-}
-// v's half of clamp100_body on a wave of its own.  The clamp is a select per component that leaves a
-// component inside +-100 (and a NaN) as it is, so which wave mates send the wave into it changes no lane's
-// value: voting on v alone here and on ω alone there gives every lane what the common vote gave it.
-template <typename Real>
-__device__ __forceinline__ void clamp100_vel(V3<Real>& v, const ChainK<Real>& K) {
-    if constexpr (sizeof(Real) == 8) {
-        const Real c = K.c100;
-        const bool bx = fabs_(v.x) > c, by = fabs_(v.y) > c, bz = fabs_(v.z) > c;
-        if (__builtin_expect(__any(bx | by | bz), 0)) v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
-    } else {
-        v = v3(clamp100_(v.x), clamp100_(v.y), clamp100_(v.z));
-    }
-}
-
-// true where the four prop heights are literal zeros (the compiled-in constants: cf2x_consts); device
-// constants, whatever their values, give false
-template <typename Real>
-__device__ __forceinline__ bool flat_props(const HoverConst<Real>& a) {
-    bool flat = true;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) flat = flat && __builtin_constant_p(a.pz[i]) && a.pz[i] == Real(0);
-    return flat;
-}
-
-// One Bullet stepSimulation of one drone after the reference's force calls, ω in the body frame
-// (st.wb; b.w is not touched: the caller rotates st.wb back once after the last sub-step).  On entry
-// st holds the thrust axis, the current z axis, R^T zs and |wb| of the pose b.q; on exit those of the
-// new pose.  Returns true if the plane contact model acted.
-// K: the chain's literal constants (pinned into VGPRs by the fp64 caller, ChainK)
-// EXT: Fext, one more world-frame force through the centre of mass (MultiHoverAviary's downwash), is
-// added to the force sum; without it (HoverAviary) the argument is not read
-// ROT (plain PYB without EXT): the rotational half alone.  Nothing translational feeds the rotation, so b.pos
-// and b.vel are neither read nor written, the plane contact is not tested (returns false) and the caller
-// runs pyb_trans_substep elsewhere, from st.zs of each sub-step and st.zc behind it
-// POSE (with ROT): st.zs and st.zc are not formed either (nothing in the rotational half reads them: m3 comes
-// from the increment); whoever runs the translational half forms them from the quaternions, b.q behind each call
-template <typename Real, int PH, bool EXT = false, bool ROT = false, bool POSE = false>
-__device__ __forceinline__ bool pyb_substep(const HoverConst<Real>& a, Body<Real>& b, Chain<Real>& st,
-                                            const Real rpm[4], Real sum_f, V3<Real> P, Real tau_z,
-                                            const ChainK<Real>& K, V3<Real> Fext = V3<Real>{}, Real* vxy = nullptr) {
-    constexpr bool GND = (PH == ADRP_PHYS_PYB_GND || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
-    constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
-    constexpr bool FULL = DRAG && !GND;   // the only mode that multiplies by whole matrices
-    static_assert(!ROT || (!GND && !DRAG && !EXT), "the rotational half stands alone in plain PYB only");
-    static_assert(!POSE || ROT, "the z axes are left out of the rotational half only");
-    // _physics: 4 prop forces + z torque on link 4, LINK_FRAME, cached basis
-    const V3<Real> zs = st.zs;
-    V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
-    const V3<Real> m3 = st.m3;
-    // P x m3 + tau_z m3.  Flat props (literal pz = 0, the compiled-in drone): P.z is +0, and fma(P.y, m3.z,
-    // -(0 m3.y)) = P.y m3.z, fma(0, m3.x, c) = c but for the sign of an exact zero, so the two P.z products go
-    // (tests/test_hover_offchain_gpu.py holds the compiled kernel to the generic one, which keeps them)
-    V3<Real> nb = flat_props(a)
-                      ? v3(fmx(tau_z, m3.x, P.y * m3.z), fmx(tau_z, m3.y, -(P.x * m3.z)),
-                           fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))))
-                      : v3(fmx(tau_z, m3.x, fmx(P.y, m3.z, -(P.z * m3.y))), fmx(tau_z, m3.y, fmx(P.z, m3.x, -(P.x * m3.z))),
-                           fmx(tau_z, m3.z, fmx(P.x, m3.y, -(P.y * m3.x))));
-    if constexpr (GND) {
-        // getLinkStates(computeForwardKinematics=1) refreshes the cached basis first (so the drag
-        // below is applied in the current basis)
-        const Real sqx = b.q.x * b.q.x, sqy = b.q.y * b.q.y, sqz = b.q.z * b.q.z, squ = b.q.w * b.q.w;
-        const Real sarg = Real(-2) * (b.q.x * b.q.z - b.q.w * b.q.y);
-        const Real den = squ - sqx - sqy + sqz, num = Real(2) * (b.q.y * b.q.z + b.q.w * b.q.x);
-        // |roll| < pi/2 and |pitch| < pi/2 of getEulerFromQuaternion (BaseAviary.py:749)
-        const bool gate = fabs_(sarg) < Real(0.99999) && (den > Real(0) || (den == Real(0) && num == Real(0)));
-        if (gate) {
-            Real sg = 0;
-            V3<Real> G = v3(Real(0), Real(0), Real(0));
-            const V3<Real> r2 = row2_fm(b.q);   // prop heights: the third row of the current pose's matrix
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                Real h = b.pos.z + r2.x * a.px[i] + r2.y * a.py[i] + r2.z * a.pz[i];
-                h = h < a.gnd_clip ? a.gnd_clip : h;
-                const Real k = a.prop_r4 * rcp_(h);
-                const Real g = a.gnd_kf * rpm[i] * rpm[i] * k * k;
-                sg += g;
-                G = G + v3(g * a.px[i], g * a.py[i], g * a.pz[i]);
-            }
-            Fw = Fw + sg * st.zc;
-            nb = nb + v3(G.y, -G.x, Real(0));
-        }
-    }
-    if constexpr (DRAG) {
-        Real s = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s += b.prev_rpm[i];
-        s = s * Real(0.10471975511965977);  // sum(2*pi*rpm/60)
-        const V3<Real> dw = v3(-a.drag[0] * s * b.vel.x, -a.drag[1] * s * b.vel.y, -a.drag[2] * s * b.vel.z);
-        // np.dot(base_rot.T, drag_factors * vel), applied in the cached link basis
-        if constexpr (GND) Fw = Fw + dw;
-        else Fw = Fw + mul(st.Rs, mulT(st.R, dw));
-    }
-    if constexpr (EXT) Fw = Fw + Fext;
-    // ---- Bullet: forwardKinematics, ABA of the floating base, semi-implicit Euler ----
-    V3<Real> wb = st.wb;
-    const V3<Real> Iw = v3(a.ixx * wb.x, a.iyy * wb.y, a.izz * wb.z);
-    const Real kw = K.k004 + K.k004 * st.wn;
-    // nb - kw Iw - wb x Iw
-    const V3<Real> rhs = v3(fmx(wb.z, Iw.y, fmx(-wb.y, Iw.z, fmx(-kw, Iw.x, nb.x))),
-                            fmx(wb.x, Iw.z, fmx(-wb.z, Iw.x, fmx(-kw, Iw.y, nb.y))),
-                            fmx(wb.y, Iw.x, fmx(-wb.x, Iw.y, fmx(-kw, Iw.z, nb.z))));
-    V3<Real> acc{};
-    if constexpr (!ROT) {
-        const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(b.vel, b.vel), K);
-        acc = v3(fmx(-kv, b.vel.x, a.inv_mass * Fw.x), fmx(-kv, b.vel.y, a.inv_mass * Fw.y),
-                 fmx(-kv, b.vel.z, a.inv_mass * Fw.z));
-    }
-    // ω' = ω + dt R I^-1 rhs in the body frame of the pose the exp map is about to leave: the map
-    // rotates about ω' itself, so R'^T ω' = R^T ω' and the body-frame update needs no rotation
-    wb = v3(fmx(st.dti.x, rhs.x, wb.x), fmx(st.dti.y, rhs.y, wb.y), fmx(st.dti.z, rhs.z, wb.z));
-    if constexpr (!ROT) b.vel = v3(b.vel.x + a.dt * acc.x, b.vel.y + a.dt * acc.y, b.vel.z + a.dt * acc.z);
-    Real ang = hsqrt_nn_(dot(wb, wb), K);
-    clamp100_body<Real, !ROT>(b.q, wb, ang, b.vel, K);
-    st.wb = wb;
-    st.wn = ang;
-    // (vxy: nothing in a sub-step reads pos.x / pos.y, so the caller may take this sub-step's horizontal
-    // velocity instead and run the same two sums itself afterwards, pyb_chain)
-    if constexpr (ROT) {
-    } else if (vxy) {
-        vxy[0] = b.vel.x; vxy[1] = b.vel.y;
-        b.pos.z = fmx(a.dt, b.vel.z, b.pos.z);
-    } else {
-        b.pos = v3(fmx(a.dt, b.vel.x, b.pos.x), fmx(a.dt, b.vel.y, b.pos.y), fmx(a.dt, b.vel.z, b.pos.z));
-    }
-    // exp-map quaternion update (btMultiBody::stepPositionsMultiDof)
-    if (ang > a.ang_max) ang = a.ang_max;          // |w| dt > ANGULAR_MOTION_THRESHOLD
-    // sin(|w| dt / 2) / |w| = (dt / 2) sinc(|w| dt / 2): no reciprocal, and Bullet's small-angle
-    // form (|w| < 0.001: 0.5 dt - dt^3 |w|^2 / 48) is the same series to rounding
-    Real sinc, ch;
-    expmap_sinc_cos(Real(0.5) * ang * a.dt, &sinc, &ch, K);
-    const Real sc = (Real(0.5) * a.dt) * sinc;
-    const V3<Real> ax = sc * wb;
-    // (R ax, ch) (x) q0 = q0 (x) (ax, ch): the world-frame increment on the left is the body-frame one on the right
-    const Q4<Real> q0 = b.q;
-    const Q4<Real> q1 = {ch * q0.x + ax.x * q0.w + ax.z * q0.y - ax.y * q0.z,
-                         ch * q0.y + ax.y * q0.w + ax.x * q0.z - ax.z * q0.x,
-                         ch * q0.z + ax.z * q0.w + ax.y * q0.x - ax.x * q0.y,
-                         ch * q0.w - ax.x * q0.x - ax.y * q0.y - ax.z * q0.z};
-    const Real inv = quat_inv_norm(q1.x * q1.x + q1.y * q1.y + q1.z * q1.z + q1.w * q1.w, K);
-    // the basis cached by this step's forwardKinematics is the pre-integration pose
-    if (a.link_lag) {
-        b.ql = q0;
-        if constexpr (!POSE) st.zs = st.zc;
-        // R'^T col2(R) = third row of the rotation of the increment d = (ax, ch) / |q1|
-        const Real s2 = (inv + inv) * inv;
-        st.m3 = v3(s2 * (ax.x * ax.z - ch * ax.y), s2 * (ax.y * ax.z + ch * ax.x),
-                   Real(1) - s2 * (ax.x * ax.x + ax.y * ax.y));
-        if constexpr (FULL) st.Rs = st.R;
-    }
-    b.q = {q1.x * inv, q1.y * inv, q1.z * inv, q1.w * inv};
-    if constexpr (FULL) {
-        st.R = rot_fm(b.q);
-        st.zc = col2(st.R);
-    } else if constexpr (!POSE) {
-        st.zc = col2_fm(b.q);
-    }
-    if (!a.link_lag) {
-        if constexpr (!POSE) st.zs = st.zc;
-        st.m3 = v3(Real(0), Real(0), Real(1));
-        if constexpr (FULL) st.Rs = st.R;
-    }
-    // plane contact model: non-penetration, no inward velocity.
-    // lowest point of the body cylinder: cos(tilt) = R22, sin(tilt) = |(R02, R12)|.  It is at
-    // least z + zoff - hh - r below the centre, so a wave whose drones are all higher than that
-    // skips the exact test (same result)
-    if constexpr (ROT) return false;
-    if (__builtin_expect(__any(b.pos.z + a.coll_zoff <= a.coll_hh + a.coll_r + Real(1e-6)), 0)) {
-        const Real low = b.pos.z + a.coll_zoff - a.coll_hh * fabs_(st.zc.z) -
-                         a.coll_r * hsqrt_nn_(st.zc.x * st.zc.x + st.zc.y * st.zc.y);
-        if (low < Real(0)) {
-            b.pos.z -= low;
-            if (b.vel.z < Real(0)) b.vel.z = Real(0);
-            return true;
-        }
-    }
-    return false;
-}
-
-// The translational half of pyb_substep<ROT = false> in plain PYB without an external force, for a wave that
-// carries pos and vel alone (the hover step's translation wave): the same expressions in the same order, so
-// the same bits.  zs: the sub-step's thrust axis.  The plane contact is the caller's (it needs the pose behind
-// the sub-step): pyb_trans_contact.
-template <typename Real>
-__device__ __forceinline__ void pyb_trans_substep(const HoverConst<Real>& a, V3<Real>& pos, V3<Real>& vel, V3<Real> zs,
-                                                  Real sum_f, const ChainK<Real>& K) {
-    const V3<Real> Fw = v3(sum_f * zs.x, sum_f * zs.y, sum_f * zs.z - a.mass * a.gravity);
-    const Real kv = K.k004 + K.k004 * hsqrt_nn_(dot(vel, vel), K);
-    const V3<Real> acc = v3(fmx(-kv, vel.x, a.inv_mass * Fw.x), fmx(-kv, vel.y, a.inv_mass * Fw.y),
-                            fmx(-kv, vel.z, a.inv_mass * Fw.z));
-    vel = v3(vel.x + a.dt * acc.x, vel.y + a.dt * acc.y, vel.z + a.dt * acc.z);
-    clamp100_vel(vel, K);
-    pos = v3(fmx(a.dt, vel.x, pos.x), fmx(a.dt, vel.y, pos.y), fmx(a.dt, vel.z, pos.z));
-}
-// pyb_substep's wave-uniform guard of the plane contact test, and the test itself with zc, the third column
-// of the pose behind the sub-step
-template <typename Real>
-__device__ __forceinline__ bool pyb_trans_near_plane(const HoverConst<Real>& a, V3<Real> pos) {
-    return __builtin_expect(__any(pos.z + a.coll_zoff <= a.coll_hh + a.coll_r + Real(1e-6)), 0);
-}
-template <typename Real>
-__device__ __forceinline__ bool pyb_trans_contact(const HoverConst<Real>& a, V3<Real>& pos, V3<Real>& vel, V3<Real> zc) {
-    const Real low = pos.z + a.coll_zoff - a.coll_hh * fabs_(zc.z) -
-                     a.coll_r * hsqrt_nn_(zc.x * zc.x + zc.y * zc.y);
-    if (low < Real(0)) {
-        pos.z -= low;
-        if (vel.z < Real(0)) vel.z = Real(0);
-        return true;
-    }
-    return false;
-}
-
-// Physics.DYN (BaseAviary.py:822-896): explicit model, forward Euler, _integrateQ
-template <typename Real>
-__device__ __forceinline__ void dyn_substep(const HoverConst<Real>& a, Body<Real>& b, const Real rpm[4]) {
-    const M3<Real> R = rot(b.q);
-    Real f[4], zt[4], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[i] = rpm[i] * rpm[i] * a.kf;
-        zt[i] = rpm[i] * rpm[i] * a.km;
-        sum += f[i];
-    }
-    const V3<Real> zb = col2(R);
-    const V3<Real> force_w = v3(sum * zb.x, sum * zb.y, sum * zb.z - a.gravity * a.mass);
-    const Real tz = -zt[0] + zt[1] - zt[2] + zt[3];
-    const Real tx = (f[0] + f[1] - f[2] - f[3]) * a.dyn_arm;
-    const Real ty = (-f[0] + f[1] + f[2] - f[3]) * a.dyn_arm;
-    const V3<Real> rr = b.w;
-    const V3<Real> tq = v3(tx, ty, tz) - cross(rr, v3(a.ixx * rr.x, a.iyy * rr.y, a.izz * rr.z));
-    const V3<Real> rdd = v3(tq.x * a.inv_ixx, tq.y * a.inv_iyy, tq.z * a.inv_izz);
-    b.vel = b.vel + a.dt * (a.inv_mass * force_w);
-    b.w = rr + a.dt * rdd;
-    b.pos = b.pos + a.dt * b.vel;
-    const V3<Real> w = b.w;
-    const Real wn = hsqrt_(dot(w, w));
-    if (!(wn <= Real(1e-8))) {  // np.isclose(omega_norm, 0)
-        const Real th = wn * a.dt * Real(0.5);
-        Real s, c;
-        if (th <= Real(0.39269908169872414)) small_sincos(th, &s, &c);
-        else sincos_(th, &s, &c);
-        const Real k = s * rcp_(wn);
-        const Q4<Real> q = b.q;
-        b.q = {c * q.x + k * (w.z * q.y - w.y * q.z + w.x * q.w),
-               c * q.y + k * (-w.z * q.x + w.x * q.z + w.y * q.w),
-               c * q.z + k * (w.y * q.x - w.x * q.y + w.z * q.w),
-               c * q.w + k * (-w.x * q.x - w.y * q.y - w.z * q.z)};
-    }
-    b.angv = mul(R, b.w);   // resetBaseVelocity(vel, rotation @ rpy_rates)
-}
-
-// BaseAviary.reset -> _housekeeping (+ the optional init_noise extension), Real precision
-// (a: the reset distribution; gid, tag: the Philox stream of the drone being reset)
-template <typename Real>
-__device__ __forceinline__ void hover_reset_draw(const HoverReset<Real>& a, uint64_t seed, uint64_t gid, uint32_t tag,
-                                                 const HoverConst<Real>& C, Body<Real>& b, int32_t& sc, int32_t& ep) {
-    const U4 r0 = draw(seed, gid, uint32_t(ep), tag, 0);
-    const U4 r1 = draw(seed, gid, uint32_t(ep), tag, 1);
-    const U4 r2 = draw(seed, gid, uint32_t(ep), tag, 2);
-    const uint32_t w0[4] = {r0.a, r0.b, r0.c, r0.d}, w1[4] = {r1.a, r1.b, r1.c, r1.d},
-                   w2[4] = {r2.a, r2.b, r2.c, r2.d};
-    Real p[3], e_[3], v[3], om[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p[k] = a.init_xyz[k] + a.n_xyz[k] * (Real(2) * u01r<Real>(w0[k]) - Real(1));
-        e_[k] = a.init_rpy[k] + a.n_rpy[k] * (Real(2) * u01r<Real>(w1[k]) - Real(1));
-        v[k] = a.n_vel[k] * (Real(2) * u01r<Real>(w2[k]) - Real(1));
-    }
-    om[0] = a.n_om[0] * (Real(2) * u01r<Real>(w0[3]) - Real(1));
-    om[1] = a.n_om[1] * (Real(2) * u01r<Real>(w1[3]) - Real(1));
-    om[2] = a.n_om[2] * (Real(2) * u01r<Real>(w2[3]) - Real(1));
-    b.q = quat_from_euler_fast<Real>(e_[0], e_[1], e_[2]);
-    b.pos = v3(p[0], p[1], p[2]);
-    b.ql = b.q;
-    b.vel = v3(v[0], v[1], v[2]);
-    if (C.physics == ADRP_PHYS_DYN) {
-        b.w = mulT(rot(b.q), v3(om[0], om[1], om[2]));
-        b.angv = v3(om[0], om[1], om[2]);
-    } else {
-        b.w = v3(om[0], om[1], om[2]);
-        b.angv = v3(Real(0), Real(0), Real(0));
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
-    sc = 0;
-    ep += 1;
-}
-template <typename Real>
-__device__ __forceinline__ void hover_reset_state(const HoverArgs<Real>& args, const HoverConst<Real>& C, int e,
-                                                  Body<Real>& b, int32_t& sc, int32_t& ep) {
-    hover_reset_draw(*args.r, args.seed, uint64_t(args.env_offset + e), TAG_HOVER_RESET, C, b, sc, ep);
-}
-
-// euler_xyz_fast_u's angles one at a time: the same arguments (euler_args, contraction pinned, so the
-// same bits) and the same wave-uniform gimbal-lock branch, for the HELP kernel's angle helpers
-template <typename Real>
-__device__ __forceinline__ Real euler_roll_u(Q4<Real> q) {
-    if (__builtin_expect(__any(fabs_(euler_sarg(q)) >= Real(0.99999)), 0)) return euler_xyz_fast(q).x;
-    const EulerArgs<Real> a = euler_args(q);
-    return fatan2_(a.y0, a.x0);
-}
-template <typename Real>
-__device__ __forceinline__ Real euler_pitch_u(Q4<Real> q) {
-    const Real sarg = euler_sarg(q);
-    if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) return euler_xyz_fast(q).y;
-    return fasin_(sarg);
-}
-template <typename Real>
-__device__ __forceinline__ Real euler_yaw_u(Q4<Real> q) {
-    if (__builtin_expect(__any(fabs_(euler_sarg(q)) >= Real(0.99999)), 0)) return euler_xyz_fast(q).z;
-    const EulerArgs<Real> a = euler_args(q);
-    return fatan2_(a.y2, a.x2);
-}
-
-// The same three for the fp64 angle helper waves, by the lean forms (adrp_device.h, AngK: the wave's pinned
-// constants).  One vote sends the whole wave to the function above when any lane is outside the lean forms'
-// domain -- NaN, gimbal lock, an atan2 argument pair that is not safely away from zero and infinity -- so
-// every input gives the bits it gives above; on the others the lean forms are the same operations.
-__device__ __forceinline__ double euler_roll_lean(Q4<double> q, const AngK& k) {
-    const EulerArgs<double> a = euler_args(q);
-    const bool ok = fabs_(a.sarg) < k.lim && f64::atan2_lean_ok(a.y0, a.x0, k);
-    if (__builtin_expect(__any(!ok), 0)) return euler_roll_u(q);
-    return f64::atan2_lean<false>(a.y0, a.x0, k);
-}
-__device__ __forceinline__ double euler_pitch_lean(Q4<double> q, const AngK& k) {
-    const double sarg = euler_sarg(q);
-    if (__builtin_expect(__any(!(fabs_(sarg) < k.lim)), 0)) return euler_pitch_u(q);
-    return f64::asin_lean(sarg, k);
-}
-__device__ __forceinline__ double euler_yaw_lean(Q4<double> q, const AngK& k) {
-    const EulerArgs<double> a = euler_args(q);
-    const bool ok = fabs_(a.sarg) < k.lim && f64::atan2_lean_ok(a.y2, a.x2, k);
-    if (__builtin_expect(__any(!ok), 0)) return euler_yaw_u(q);
-    return f64::atan2_lean<false>(a.y2, a.x2, k);
-}
-
-// The chain wave's tilt test without an angle (adrp_device.h, TruncK): false if the lane is unsure, else
-// over = |roll| > 0.4 || |pitch| > 0.4 as the float64 angles of euler_xyz_fast_u decide it
-__device__ __forceinline__ bool trunc_from_quat(Q4<double> q, const TruncK& k, bool& over) {
-    const EulerArgs<double> a = euler_args(q);
-    const double as = fabs_(a.sarg), ay = fabs_(a.y0);
-    const bool p_over = as > k.s_hi, r_over = ay > k.t_hi * a.x0;
-    const bool p_sure = p_over || as < k.s_lo, r_sure = r_over || ay < k.t_lo * a.x0;
-    over = p_over || r_over;
-    return p_sure && r_sure && a.x0 > 0.0 && as < k.lim;
-}
-__device__ __forceinline__ bool trunc_from_quat(Q4<float>, const TruncK&, bool&) { return false; }   // (fp64 kernels only)
-
-// E = 1 persistent step (SPLIT): lane L evaluates Euler angle min(L, 2) of the (duplicated) env with
-// ONE atan2 -- roll (y0, x0), pitch (sarg, sqrt((1 - sarg)(1 + sarg)), the atan2 form of fasin_),
-// yaw (y2, x2) -- and the three come back by readlane: the same arguments as euler_xyz_fast_u
-// (euler_args), so the same bits, for one atan2 on the chain instead of three
-template <typename Real>
-__device__ __forceinline__ Real euler_axis_u(Q4<Real> q, int ax) {
-    const EulerArgs<Real> a = euler_args(q);
-    const Real sarg = a.sarg;
-    if (__builtin_expect(__any(fabs_(sarg) >= Real(0.99999)), 0)) {
-        const V3<Real> r = euler_xyz_fast(q);
-        return ax == 0 ? r.x : (ax == 1 ? r.y : r.z);
-    }
-    const Real y0 = a.y0, x0 = a.x0, y2 = a.y2, x2 = a.x2;
-    Real x1;
-    if constexpr (sizeof(Real) == 8) x1 = f64::sqrt((1.0 - sarg) * (1.0 + sarg));
-    else x1 = __builtin_amdgcn_sqrtf((1.0f - sarg) * (1.0f + sarg));
-    const Real yy = ax == 0 ? y0 : (ax == 1 ? sarg : y2), xx = ax == 0 ? x0 : (ax == 1 ? x1 : x2);
-    return fatan2_(yy, xx);
-}
-__device__ __forceinline__ float readlane_r(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ double readlane_r(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-// hover_obs12 with the angles dealt over lanes 0..2 (every lane holds the same env)
-template <typename Real>
-__device__ __forceinline__ V3<Real> hover_obs12_split(const HoverConst<Real>& a, const Body<Real>& b, float o[12]) {
-    const int l = int(threadIdx.x) & 63;
-    const Real ang = euler_axis_u(b.q, l < 2 ? l : 2);
-    const V3<Real> rpy = v3(readlane_r(ang, 0), readlane_r(ang, 1), readlane_r(ang, 2));
-    const V3<Real> w = a.physics == ADRP_PHYS_DYN ? b.angv : b.w;
-    o[0] = float(b.pos.x); o[1] = float(b.pos.y); o[2] = float(b.pos.z);
-    o[3] = float(rpy.x);   o[4] = float(rpy.y);   o[5] = float(rpy.z);
-    o[6] = float(b.vel.x); o[7] = float(b.vel.y); o[8] = float(b.vel.z);
-    o[9] = float(w.x);     o[10] = float(w.y);    o[11] = float(w.z);
-    return rpy;
-}
-
-template <typename Real>
-__device__ __forceinline__ V3<Real> hover_obs12(const HoverConst<Real>& a, const Body<Real>& b, float o[12]) {
-    const V3<Real> rpy = euler_xyz_fast_u(b.q);
-    const V3<Real> w = a.physics == ADRP_PHYS_DYN ? b.angv : b.w;
-    o[0] = float(b.pos.x); o[1] = float(b.pos.y); o[2] = float(b.pos.z);
-    o[3] = float(rpy.x);   o[4] = float(rpy.y);   o[5] = float(rpy.z);
-    o[6] = float(b.vel.x); o[7] = float(b.vel.y); o[8] = float(b.vel.z);
-    o[9] = float(w.x);     o[10] = float(w.y);    o[11] = float(w.z);
-    return rpy;
-}
-
-// one obs row [12 kinematic | B x A action ring, oldest first] from registers
-template <int A, int B>
-__device__ __forceinline__ void write_row(float* row, const float o12[12], const float (&ring)[B][A], int head1) {
-    if constexpr (A == 4) {
-        float4* r4 = reinterpret_cast<float4*>(row);
-        r4[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-        r4[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-        r4[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-#pragma unroll
-        for (int p = 0; p < B; ++p) {          // physical slot p -> logical position k
-            int k = p - head1;
-            k += k < 0 ? B : 0;
-            r4[3 + k] = make_float4(ring[p][0], ring[p][1], ring[p][2], ring[p][3]);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) row[k] = o12[k];
-#pragma unroll
-        for (int p = 0; p < B; ++p) {
-            int k = p - head1;
-            k += k < 0 ? B : 0;
-#pragma unroll
-            for (int j = 0; j < A; ++j) row[12 + k * A + j] = ring[p][j];
-        }
-    }
-}
-
-// generic-B variant: the ring part is copied from HBM in logical order (slot head1 = oldest);
-// the newest entry (logical B-1) is this step's action
-template <int A>
-__device__ __forceinline__ void write_row_generic(float* __restrict__ row, const float o12[12],
-                                                  const float* __restrict__ ring, int B, int E, int e, int head1,
-                                                  const float act[A], bool act_is_newest) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) row[k] = o12[k];
-    // chunks of 8 slots: all loads of a chunk in flight before its stores
-    constexpr int CH = 8;
-    int slot = head1;
-    for (int k0 = 0; k0 < B; k0 += CH) {
-        float v[CH][A];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const int k = k0 + c;
-#pragma unroll
-            for (int j = 0; j < A; ++j)
-                v[c][j] = k < B ? ((act_is_newest && k == B - 1) ? act[j] : ring[(size_t(slot) * E + e) * A + j]) : 0.0f;
-            slot = slot + 1 == B ? 0 : slot + 1;
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const int k = k0 + c;
-            if (k < B)
-#pragma unroll
-                for (int j = 0; j < A; ++j) row[12 + k * A + j] = v[c][j];
-        }
-    }
-}
-
-// DSLPIDControl.computeControl (control/DSLPIDControl.py:82-259) for the HoverAviary PID / VEL /
-// ONE_D_PID action types (BaseRLAviary.py:193-235): once per env.step, on the state at the
-// start of the step.  ctl = last_rpy 3, integral_pos_e 3, integral_rpy_e 3 (in/out).  The
-// scipy Euler round trip of the target rotation (:205, :242-244) is the identity on a proper
-// rotation, so the target basis is used directly (oracle/oracle.c orc_dslpid, pinned by
-// tests/golden/pid_golden.npz).
-template <typename Real, int CTL>
-__device__ __forceinline__ void dslpid_rpm(const HoverConst<Real>& C, const Body<Real>& b, const float* act,
-                                           Real ctl[HF_NPID], Real rpm[4]) {
-    const M3<Real> R = rot(b.q);
-    const V3<Real> rpy = euler_xyz(b.q);   // accurate: the D term scales its error by 6e5
-    V3<Real> tp, tv = v3(Real(0), Real(0), Real(0));
-    Real tyaw = 0;
-    if constexpr (CTL == ADRP_ACT_PID) {
-        // _calculateNextStep(pos, action, step_size=1) (BaseAviary.py:1112-1160)
-        const V3<Real> d = v3(Real(act[0]) - b.pos.x, Real(act[1]) - b.pos.y, Real(act[2]) - b.pos.z);
-        const Real dist = sqrt_(dot(d, d));
-        tp = dist <= Real(1) ? v3(Real(act[0]), Real(act[1]), Real(act[2])) : b.pos + (Real(1) / dist) * d;
-    } else if constexpr (CTL == ADRP_ACT_VEL) {
-        // target_vel = SPEED_LIMIT*|a3|*a[0:3]/|a[0:3]| in float32 (float32 action, NEP 50)
-#pragma clang fp contract(off)
-        tp = b.pos;
-        tyaw = rpy.z;
-        // correctly rounded float32 sqrt / division through float64 (53 >= 2*24 + 2 bits)
-        const float n = float(sqrt(double(act[0] * act[0] + act[1] * act[1] + act[2] * act[2])));
-        const float s = C.speed_limit * fabsf(act[3]);
-        if (n != 0.0f) {
-            const double dn = double(n);
-            tv = v3(Real(s * float(double(act[0]) / dn)), Real(s * float(double(act[1]) / dn)),
-                    Real(s * float(double(act[2]) / dn)));
-        }
-    } else {   // ONE_D_PID: target_pos = pos + 0.1*[0, 0, a]
-        tp = v3(b.pos.x, b.pos.y, b.pos.z + Real(0.1) * Real(act[0]));
-    }
-    // the two loops (dslpid_core.h) with DSLPIDControl's CF2X gains (:42-47) and no target rates
-    constexpr DslpidGains<Real> K = {{Real(.4), Real(.4), Real(1.25)}, {Real(.05), Real(.05), Real(.05)},
-                                     {Real(.2), Real(.2), Real(.5)}, {Real(70000), Real(70000), Real(60000)},
-                                     {Real(0), Real(0), Real(500)}, {Real(20000), Real(20000), Real(12000)}};
-    const Real tpa[3] = {tp.x, tp.y, tp.z}, tva[3] = {tv.x, tv.y, tv.z}, rates[3] = {Real(0), Real(0), Real(0)};
-    Real thrust, tq[3], pos_e[3], tt[3];
-    V3<Real> xax, yax;
-    dslpid_core<Real>(K, C.ctrl_dt, C.ctrl_hz, C.pid_grav, C.pid_inv4kf, Real(4070.3), Real(1.0 / 0.2685), R, rpy, b.pos,
-                      b.vel, tpa, tyaw, tva, rates, ctl, thrust, tq, pos_e, tt, xax, yax);
-    // CF2X mixer [[-.5,-.5,-1],[-.5,.5,1],[.5,.5,-1],[.5,-.5,1]], PWM clip, PWM -> RPM
-    const Real hr = Real(0.5) * tq[0], hp = Real(0.5) * tq[1];
-    const Real pwm[4] = {thrust - hr - hp - tq[2], thrust - hr + hp + tq[2], thrust + hr + hp - tq[2],
-                         thrust + hr - hp + tq[2]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const Real p = pwm[i] < Real(20000) ? Real(20000) : (pwm[i] > Real(65535) ? Real(65535) : pwm[i]);
-        rpm[i] = Real(0.2685) * p + Real(4070.3);
-    }
-}
-
-// ---- state field addressing ----
-// The state is [field][E]: field k of env e lies k * E * sizeof(T) bytes behind the env's field 0.  Indexed
-// as f[k * E + e] every field costs three VALU instructions (add, sign extension, 64-bit shift-add) and
-// a 64-bit address pair that lives from the loads to the stores.  Here a lane walks the fields with ONE
-// 32-bit byte offset on the uniform base pointer, the saddr + voffset form of the global instructions: a
-// v_add_u32 of the stride per field, and the offsets (one VGPR each) serve the stores again.  (field_lane:
-// the offset is opaque to the optimiser, which would otherwise rebuild off0 + k * stride per field.)
-// The offsets are 32-bit, so the form holds while every field of the block, the PID fields included, ends
-// below 4 GiB: up to kFieldOffsetMaxBytes / ((HF_NBASE + HF_NPID) sizeof(T)) envs (field_offsets_fit;
-// adrp_internal.h states the bound).  Above it the accesses keep 64-bit indices: the hover step kernel
-// has both forms and the host picks one (W32); the other callers of load_body / store_body branch on E.
-constexpr uint64_t kFieldOffsetMaxBytes = uint64_t(1) << 32;
-template <typename T>
-__host__ __device__ constexpr uint32_t field_offsets_max_envs() {
-    return uint32_t(kFieldOffsetMaxBytes / (uint64_t(HF_NBASE + HF_NPID) * sizeof(T)));
-}
-template <typename T>
-__host__ __device__ constexpr bool field_offsets_fit(int E) {
-    return __builtin_expect(uint32_t(E) <= field_offsets_max_envs<T>(), 1);
-}
-__device__ __forceinline__ uint32_t field_lane(uint32_t off) {
-    asm("" : "+v"(off));
-    return off;
-}
-// keeps the value's uses behind (and its definition before) the side-effecting statements around it
-__device__ __forceinline__ void hold(double& x) { asm volatile("" : "+v"(x)); }
-__device__ __forceinline__ void hold(float& x) { asm volatile("" : "+v"(x)); }
-// Ends the 32-bit arm of a branch on field_offsets_fit.  Both arms finish with the same loads (or stores)
-// of the same fields; without a difference at their ends the optimiser sinks those into the join with the
-// address picked per field from the two forms (a 64-bit select each), which is worse than either.
-__device__ __forceinline__ void field_form_end() { asm volatile(""); }
-template <typename T>
-__device__ __forceinline__ T& field_at(T* base, uint32_t off) {
-    return *(T*)((const char*)base + off);   // (T may be const: the byte pointer drops it for the arithmetic only)
-}
-// the last use of an offset (the stores): the address is formed behind a statement that stays in the
-// store's own block, so it is not shared with the load's block as a 64-bit pair formed above both
-template <typename T>
-__device__ __forceinline__ T& field_last(T* base, uint32_t off) {
-    asm volatile("" : "+v"(off));
-    return *(T*)((const char*)base + off);
-}
-// byte offsets o[first .. first + n) of the lane's fields first .. first + n - 1 (off0: of its field 0)
-template <int N>
-__device__ __forceinline__ void field_run(uint32_t off0, uint32_t stride, int first, int n, uint32_t (&o)[N]) {
-    uint32_t off = first ? field_lane(off0 + uint32_t(first) * stride) : off0;
-#pragma unroll
-    for (int i = 0; i < n; ++i) {
-        o[first + i] = off;
-        if (i + 1 < n) off = field_lane(off + stride);
-    }
-}
-// the offsets of one env's Body fields (those the mode reads; the others stay unset and unused)
-template <typename Real>
-struct BodyOffs {
-    uint32_t o[HF_NBASE];
-};
-template <typename Real>
-__device__ __forceinline__ BodyOffs<Real> body_offsets(int E, int e, bool lag, bool drag, bool dyn) {
-    BodyOffs<Real> r;
-    const uint32_t stride = uint32_t(E) * uint32_t(sizeof(Real)), off0 = uint32_t(e) * uint32_t(sizeof(Real));
-    field_run(off0, stride, HF_POS, HF_LAST_RPM - HF_POS, r.o);   // pos, quat, vel, omega
-    if (drag) field_run(off0, stride, HF_LAST_RPM, 4, r.o);
-    if (dyn) field_run(off0, stride, HF_ANGV, 3, r.o);
-    if (lag) field_run(off0, stride, HF_LINK_QUAT, 4, r.o);
-    return r;
-}
-
-// (kin = false: pos and vel are another wave's to load; they are left zero)
-template <typename Real>
-__device__ __forceinline__ void load_body_at(const Real* f, const BodyOffs<Real>& k, Body<Real>& b, bool lag,
-                                             bool drag, bool dyn, bool kin = true) {
-    if (kin) b.pos = v3(field_at(f, k.o[HF_POS + 0]), field_at(f, k.o[HF_POS + 1]), field_at(f, k.o[HF_POS + 2]));
-    else b.pos = v3(Real(0), Real(0), Real(0));
-    b.q = {field_at(f, k.o[HF_QUAT + 0]), field_at(f, k.o[HF_QUAT + 1]), field_at(f, k.o[HF_QUAT + 2]),
-           field_at(f, k.o[HF_QUAT + 3])};
-    if (kin) b.vel = v3(field_at(f, k.o[HF_VEL + 0]), field_at(f, k.o[HF_VEL + 1]), field_at(f, k.o[HF_VEL + 2]));
-    else b.vel = v3(Real(0), Real(0), Real(0));
-    b.w = v3(field_at(f, k.o[HF_OMEGA + 0]), field_at(f, k.o[HF_OMEGA + 1]), field_at(f, k.o[HF_OMEGA + 2]));
-    if (lag) b.ql = {field_at(f, k.o[HF_LINK_QUAT + 0]), field_at(f, k.o[HF_LINK_QUAT + 1]),
-                     field_at(f, k.o[HF_LINK_QUAT + 2]), field_at(f, k.o[HF_LINK_QUAT + 3])};
-    else b.ql = b.q;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = drag ? field_at(f, k.o[HF_LAST_RPM + i]) : Real(0);
-    if (dyn) b.angv = v3(field_at(f, k.o[HF_ANGV + 0]), field_at(f, k.o[HF_ANGV + 1]), field_at(f, k.o[HF_ANGV + 2]));
-    else b.angv = v3(Real(0), Real(0), Real(0));
-}
-template <typename Real>
-__device__ __forceinline__ void store_body_at(Real* f, const BodyOffs<Real>& k, const Body<Real>& b, bool lag,
-                                              bool drag, bool dyn) {
-    field_last(f, k.o[HF_POS + 0]) = b.pos.x; field_last(f, k.o[HF_POS + 1]) = b.pos.y; field_last(f, k.o[HF_POS + 2]) = b.pos.z;
-    field_last(f, k.o[HF_QUAT + 0]) = b.q.x; field_last(f, k.o[HF_QUAT + 1]) = b.q.y;
-    field_last(f, k.o[HF_QUAT + 2]) = b.q.z; field_last(f, k.o[HF_QUAT + 3]) = b.q.w;
-    field_last(f, k.o[HF_VEL + 0]) = b.vel.x; field_last(f, k.o[HF_VEL + 1]) = b.vel.y; field_last(f, k.o[HF_VEL + 2]) = b.vel.z;
-    field_last(f, k.o[HF_OMEGA + 0]) = b.w.x; field_last(f, k.o[HF_OMEGA + 1]) = b.w.y; field_last(f, k.o[HF_OMEGA + 2]) = b.w.z;
-    if (lag) {
-        field_last(f, k.o[HF_LINK_QUAT + 0]) = b.ql.x; field_last(f, k.o[HF_LINK_QUAT + 1]) = b.ql.y;
-        field_last(f, k.o[HF_LINK_QUAT + 2]) = b.ql.z; field_last(f, k.o[HF_LINK_QUAT + 3]) = b.ql.w;
-    }
-    if (drag) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) field_last(f, k.o[HF_LAST_RPM + i]) = b.prev_rpm[i];
-    }
-    if (dyn) {
-        field_last(f, k.o[HF_ANGV + 0]) = b.angv.x; field_last(f, k.o[HF_ANGV + 1]) = b.angv.y;
-        field_last(f, k.o[HF_ANGV + 2]) = b.angv.z;
-    }
-}
-
-template <typename Real>
-__device__ __forceinline__ void load_body(const HoverArgs<Real>& a, int e, Body<Real>& b, bool lag, bool drag,
-                                          bool dyn) {
-    const int E = a.E;
-    const Real* f = a.f;
-    if (field_offsets_fit<Real>(E)) {
-        load_body_at(f, body_offsets<Real>(E, e, lag, drag, dyn), b, lag, drag, dyn);
-        field_form_end();
-        return;
-    }
-    b.pos = v3(f[(HF_POS + 0) * E + e], f[(HF_POS + 1) * E + e], f[(HF_POS + 2) * E + e]);
-    b.q = {f[(HF_QUAT + 0) * E + e], f[(HF_QUAT + 1) * E + e], f[(HF_QUAT + 2) * E + e], f[(HF_QUAT + 3) * E + e]};
-    b.vel = v3(f[(HF_VEL + 0) * E + e], f[(HF_VEL + 1) * E + e], f[(HF_VEL + 2) * E + e]);
-    b.w = v3(f[(HF_OMEGA + 0) * E + e], f[(HF_OMEGA + 1) * E + e], f[(HF_OMEGA + 2) * E + e]);
-    if (lag) b.ql = {f[(HF_LINK_QUAT + 0) * E + e], f[(HF_LINK_QUAT + 1) * E + e], f[(HF_LINK_QUAT + 2) * E + e],
-                     f[(HF_LINK_QUAT + 3) * E + e]};
-    else b.ql = b.q;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = drag ? f[(HF_LAST_RPM + i) * E + e] : Real(0);
-    if (dyn) b.angv = v3(f[(HF_ANGV + 0) * E + e], f[(HF_ANGV + 1) * E + e], f[(HF_ANGV + 2) * E + e]);
-    else b.angv = v3(Real(0), Real(0), Real(0));
-}
-
-template <typename Real>
-__device__ __forceinline__ void store_body(const HoverArgs<Real>& a, int e, const Body<Real>& b, bool lag,
-                                           bool drag, bool dyn) {
-    const int E = a.E;
-    Real* f = a.f;
-    if (field_offsets_fit<Real>(E)) {
-        store_body_at(f, body_offsets<Real>(E, e, lag, drag, dyn), b, lag, drag, dyn);
-        field_form_end();
-        return;
-    }
-    f[(HF_POS + 0) * E + e] = b.pos.x; f[(HF_POS + 1) * E + e] = b.pos.y; f[(HF_POS + 2) * E + e] = b.pos.z;
-    f[(HF_QUAT + 0) * E + e] = b.q.x; f[(HF_QUAT + 1) * E + e] = b.q.y;
-    f[(HF_QUAT + 2) * E + e] = b.q.z; f[(HF_QUAT + 3) * E + e] = b.q.w;
-    f[(HF_VEL + 0) * E + e] = b.vel.x; f[(HF_VEL + 1) * E + e] = b.vel.y; f[(HF_VEL + 2) * E + e] = b.vel.z;
-    f[(HF_OMEGA + 0) * E + e] = b.w.x; f[(HF_OMEGA + 1) * E + e] = b.w.y; f[(HF_OMEGA + 2) * E + e] = b.w.z;
-    if (lag) {
-        f[(HF_LINK_QUAT + 0) * E + e] = b.ql.x; f[(HF_LINK_QUAT + 1) * E + e] = b.ql.y;
-        f[(HF_LINK_QUAT + 2) * E + e] = b.ql.z; f[(HF_LINK_QUAT + 3) * E + e] = b.ql.w;
-    }
-    if (drag) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[(HF_LAST_RPM + i) * E + e] = b.prev_rpm[i];
-    }
-    if (dyn) {
-        f[(HF_ANGV + 0) * E + e] = b.angv.x; f[(HF_ANGV + 1) * E + e] = b.angv.y; f[(HF_ANGV + 2) * E + e] = b.angv.z;
-    }
-}
-
-// The PYB sub-step chain of one env.step of one drone: the prop force sums of the step's RPMs, ω and the
-// thrust axis into the body frame, S sub-steps (SC > 0: compile-time count, unrolled), ω back to the
-// world frame.  ext(b, st), unless NoExtForce, gives each sub-step one more world-frame force from the
-// state at its start (every lane of the wave calls it: it may exchange across lanes).  Returns true if
-// the plane contact model acted.
-// hand(k, z), unless NoHandOff (plain PYB, no external force, SC > 0): the chain runs the rotational half of
-// every sub-step alone (pyb_substep<ROT>; b.pos and b.vel are not touched, false is returned) and hands the third
-// columns of its poses to whoever runs the translational half: k = 0 that of the cached link basis, k = 1 of
-// the pose at entry, k = s + 2 of the pose behind sub-step s.  Sub-step s takes its thrust axis from k = s with
-// the link lag, from k = s + 1 without, and its contact test from k = s + 2.  The chain only hands out: it
-// never waits for the other side.
-// Pose hand-off (ADRP_HOVER_POSE_HANDOFF): hand(k, q) takes the quaternions themselves, k = s + 2 b.q behind
-// sub-step s, and the receiver forms col2_fm(q): the z axes leave the sub-steps (pyb_substep<POSE>); the pre-loop
-// still forms zs once, for m3.  k = 0 and k = 1 would be b.ql and b.q as loaded: the receiver loads those two
-// itself, and hand(0, .) is called once ahead of the sub-steps with nothing to store.
-struct NoExtForce {};
-struct NoHandOff {};
-template <typename Real, int PH, int SC, bool DRAG, typename Ext, typename Hand = NoHandOff>
-__device__ __forceinline__ bool pyb_chain(const HoverConst<Real>& C, Body<Real>& b, const Real rpm_in[4], bool lag,
-                                          Ext ext, V3<Real>* wb_out = nullptr, Real* vxy = nullptr, Hand hand = Hand{}) {
-    constexpr bool EXT = !__is_same(Ext, NoExtForce);
-    constexpr bool HAND = !__is_same(Hand, NoHandOff);
-    constexpr bool POSE = HAND && ADRP_HOVER_POSE_HANDOFF != 0;
-    static_assert(!HAND || (!EXT && !DRAG && SC > 0 && PH == ADRP_PHYS_PYB), "the hand-off is plain PYB's");
-    // (a local copy: nothing the sub-steps store can alias it, so what depends on the RPMs alone is
-    // computed once for the unrolled sub-steps)
-    const Real rpm[4] = {rpm_in[0], rpm_in[1], rpm_in[2], rpm_in[3]};
-    Real sum_f = 0, t2 = 0;
-    V3<Real> P = v3(Real(0), Real(0), Real(0));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const Real r2 = rpm[i] * rpm[i];
-        const Real f = r2 * C.kf;
-        sum_f += f;
-        // the reference drone's props sit in the body plane: a literal pz = 0 adds f * 0 = +0 (f >= 0) to
-        // +0, so P.z stays +0 without the multiply-adds (race_pyb_substep_r's idiom; flat_props below)
-        const bool pz0 = __builtin_constant_p(C.pz[i]) && C.pz[i] == Real(0);
-        const Real fx = f * C.px[i], fy = f * C.py[i], fz = f * C.pz[i];   // (products and sums in separate
-        P = v3(P.x + fx, P.y + fy, pz0 ? P.z : P.z + fz);                  //  statements: no contraction, as before)
-        t2 += (i & 1) ? -r2 : r2;
-    }
-    const Real tau_z = t2 * C.km;    // KM*(rpm0^2 - rpm1^2 + rpm2^2 - rpm3^2), IROS sign
-    // the chain's constants in VGPRs for the whole loop (fp64: no 64-bit literal operands)
-    ChainK<Real> K = chain_consts<Real>();
-    HoverConst<Real> Cp = C;
-    if constexpr (sizeof(Real) == 8) {
-        pin_all(K);
-        // (HAND: mass, gravity, inv_mass and coll_* are the translational half's alone; leaving their pins out
-        // here measured no gain by the A/B rule, profiles/ab_hover_transwave.txt, so the list stays one)
-        pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass); pin(Cp.ang_max);
-        pin(Cp.ixx); pin(Cp.iyy); pin(Cp.izz); pin(Cp.inv_ixx); pin(Cp.inv_iyy); pin(Cp.inv_izz);
-        pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
-    }
-    // into the body frame: ω, the thrust axis (third column of the cached link basis) and its
-    // body coordinates; the loop carries these, not the matrices
-    Chain<Real> st{};
-    {
-        const M3<Real> R = rot_fm(b.q);
-        const M3<Real> Rs = lag ? rot_fm(b.ql) : R;
-        st.wb = mulT(R, b.w);
-        st.zc = col2(R);
-        st.zs = col2(Rs);
-        st.m3 = lag ? mulT(R, st.zs) : v3(Real(0), Real(0), Real(1));
-        if constexpr (DRAG) {
-            st.R = R;
-            st.Rs = Rs;
-        }
-    }
-    st.wn = hsqrt_nn_(dot(b.w, b.w), K);
-    st.dti = v3(Cp.dt * Cp.inv_ixx, Cp.dt * Cp.inv_iyy, Cp.dt * Cp.inv_izz);
-    if constexpr (POSE) {
-        hand(0, b.q);   // (k = 0, 1 are state fields as loaded, which the receiver loads itself: the call marks the head)
-    } else if constexpr (HAND) {
-        hand(0, st.zs);
-        hand(1, st.zc);
-    }
-    bool touched = false;
-    // vxy (SC > 0, no external force): the horizontal position is left at its value before the chain and the
-    // SC sub-steps' horizontal velocities come back in vxy[2 s], vxy[2 s + 1]: the caller runs
-    // pos.x = fma(dt, vxy[2 s], pos.x), likewise y, in order (pos_xy_sums: the same operations, the same bits)
-    auto substep = [&](int s) {
-        if constexpr (POSE) {
-            pyb_substep<Real, PH, false, true, true>(Cp, b, st, rpm, sum_f, P, tau_z, K);
-            hand(s + 2, b.q);
-        } else if constexpr (HAND) {
-            pyb_substep<Real, PH, false, true>(Cp, b, st, rpm, sum_f, P, tau_z, K);
-            hand(s + 2, st.zc);
-        } else if constexpr (EXT) touched |= pyb_substep<Real, PH, true>(Cp, b, st, rpm, sum_f, P, tau_z, K, ext(b, st));
-        else touched |= pyb_substep<Real, PH>(Cp, b, st, rpm, sum_f, P, tau_z, K, V3<Real>{}, vxy ? vxy + 2 * s : nullptr);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) b.prev_rpm[i] = rpm[i];  // last_clipped_action
-    };
-    if constexpr (SC > 0) {
-#pragma unroll
-        for (int s = 0; s < SC; ++s) substep(s);
-    } else {
-        for (int s = 0; s < C.S; ++s) substep(s);
-    }
-    // state, obs and the stored link_quat stay in the world frame (wb_out: the caller rotates back itself,
-    // b.w = rot_fm(b.q) wb, where it has a wait to fill)
-    if (wb_out) *wb_out = st.wb;
-    else b.w = mul(rot_fm(b.q), st.wb);
-    return touched;
-}
 
 // ------------------------------------------------------------------------------------------
 // env.step kernel: lane = env; B (ring length) is a template parameter so the ring lives
 // in registers
 // ------------------------------------------------------------------------------------------
+constexpr int kResetFields = 16; // pos 3, quat 4, vel 3, w 3, angv 3 of a reset state (HELP)
 // obs rows staged in LDS, then written as one contiguous, fully coalesced block of
 // 64 rows (the row-per-lane float4 stores leave partial 64-B lines: +18 % write traffic)
 constexpr int kRowF4 = 18;        // 72 floats = 18 float4 per obs row (A = 4, B = 15)
+constexpr int kResetObs = kStepBlock * kRowF4;   // ANG: behind the 64 rows, the reset obs as three float4 per env
+// fp64 HELP kernels: two more helper waves beside the reset helper compute the obs row's pitch and yaw
+// from the chain's final quaternion, and the reset helper, idle by then, the roll; the chain meanwhile
+// rotates ω back to the world frame, converts the row and computes the reward
+// (float64 only: in float32 the two extra barriers cost more than the two atan2 they take off the
+// chain, +1.2 % against -1.2 % in float64, A/B round 6)
+template <typename Real>
+constexpr bool angle_helpers() { return sizeof(Real) == 8; }
+template <typename Real>
+constexpr int help_waves() { return angle_helpers<Real>() ? 3 : 1; }   // helper waves of a HELP workgroup
 
-template <int A, int B>
-__device__ __forceinline__ void stage_row(float4* lds_row, const float o12[12], const float (&ring)[B][A], int head1) {
-    lds_row[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-    lds_row[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-    lds_row[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-#pragma unroll
-    for (int p = 0; p < B; ++p) {
-        int k = p - head1;
-        k += k < 0 ? B : 0;
-        lds_row[3 + k] = make_float4(ring[p][0], ring[p][1], ring[p][2], ring[p][3]);
+// The quaternion slots of the pose hand-off and their marks (a view of StepLds's tw_q / tw_mark), TW kernels.
+// With plain PYB and no external force the translational half of a sub-step (force, |v|, velocity and its
+// clamp, position, plane contact) feeds nothing back into the rotation; all it takes from there is the thrust
+// axis, which with the link lag is the z axis of the pose TWO sub-steps back.  Wave 3, the yaw helper,
+// otherwise idle before barrier A, runs that half for the chain's lanes (hover_trans_wave):
+//   the chain (pyb_chain's hand-off) writes the quaternion of each of its poses, which it holds anyway for the
+//   next quaternion product, into slot k as two 16-byte halves (k = s + 2: the pose behind sub-step s), then
+//   mark[k].  It only writes: no load of pos / vel, no wait, no poll before A.  One wave's LDS operations
+//   complete in order, so the mark is visible after the data.  (LDS keeps whatever the last workgroup on the
+//   CU left: wave 3 clears the marks and waits for the clears to land ahead of a bare s_barrier that the helper
+//   waves pass at their head and the chain wave ahead of its first slot write: the head barrier.)
+//   wave 3 forms the z axis at each read, thrust axis and contact test alike: col2_fm, the chain's own
+//   expression on the chain's own bits.  Slots 0 and 1, the cached link basis and the pose at entry, are state
+//   fields as loaded: wave 3 loads them itself beside pos / vel and needs no mark for them, q holds slots
+//   2 .. SC + 1 alone.
+// The marks are one word per slot, never per lane or per value: a NaN, gimbal-lock or clamped lane is stored
+// and marked like any other.  Nobody waits forever: wave 3's clear of all kSlots mark words lands before the
+// head barrier and no mark is written ahead of that barrier; behind it the chain writes every one of its marks
+// without a wait, a poll or a barrier of its own before A, and wave 3 waits for chain marks alone.  The wait
+// graph is chain -> wave 3, no cycle, and every polling wave reaches A whatever the data holds.
+// The marks are relaxed workgroup-scope atomics (plain ds_read / ds_write, no s_waitcnt of their own); the
+// empty asm keeps the compiler from moving the data accesses across them, the LDS keeps a wave's order.
+template <typename Real, int SC>
+struct PoseSlots {
+    using Real2 = Real __attribute__((ext_vector_type(2)));
+    static constexpr int kSlots = SC + 2;
+    Real2* q;     // [2 (k - 2) + half][lane]
+    int* mark;    // [k]
+    // wave 3, ahead of the head barrier: the marks cleared, and the clears landed
+    __device__ __forceinline__ void clear(int tl) const {
+        if (tl < kSlots) __hip_atomic_store(&mark[tl], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the clears are in LDS
     }
-}
+    // The head barrier: no mark of this launch is written before every clear.  The chain's sits ahead of its
+    // first LDS write and behind its loads and the pre-loop: the translation wave's lgkmcnt(0) in front of the
+    // barrier also covers that wave's kernel-argument loads, which come in cold (later than the chain's state
+    // loads), and by now they have
+    __device__ __forceinline__ static void head() { __builtin_amdgcn_s_barrier(); }
+    __device__ __forceinline__ void wait(int k) const {   // one LDS word per poll; the chain wave is co-resident and always arrives
+        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&mark[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0)
+            __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");
+    }
+    __device__ __forceinline__ V3<Real> zaxis(int k, int tl) const {   // the z axis of the pose in slot k
+        const Real2 xy = q[(2 * k - 4) * kStepBlock + tl], zw = q[(2 * k - 3) * kStepBlock + tl];
+        return col2_fm(Q4<Real>{Real(xy.x), Real(xy.y), Real(zw.x), Real(zw.y)});
+    }
+    __device__ __forceinline__ void pose(int k, Q4<Real> p) const {   // the chain wave's hand-off (stores only)
+        const int tl = threadIdx.x;
+        Real2 xy, zw;
+        xy.x = p.x; xy.y = p.y; zw.x = p.z; zw.y = p.w;
+        q[(2 * k - 4) * kStepBlock + tl] = xy;
+        q[(2 * k - 3) * kStepBlock + tl] = zw;
+        asm volatile("" ::: "memory");
+        __hip_atomic_store(&mark[k], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+};
+
+// The step kernel's LDS, by what sizes it.
+//   rows       STG: the 64 staged obs rows; ANG: behind them the reset obs of the block's envs as three float4
+//              per env (kResetObs), which the helper waves' copy-out takes whole
+//   rs_body    HELP: the reset helper's next-episode states, [kResetFields][lane]; rs_obs: their obs (fp32)
+//   ang_*      ANG: the chain's final quaternion for the angle helpers, and their angles back for the unsure
+//              tilt test.  TW kernels keep the quaternion in the four rows of tw_out that were unused, so that
+//              three workgroups still fit the CU's 160 KB
+//   done_*     ANG: one byte per lane (the env is done), the done lanes at their rank, their count
+//   tw_*       TW: PoseSlots' storage; the translation wave's final pos / vel, indexed as rs_body is (the chain
+//              takes the six values behind A from there or, for a done lane, from rs_body), and its flag byte
+//              per lane: terminated, a position limit passed
+// A view: the arrays themselves are hover_step_body's __shared__ variables, one each, so that a kernel's LDS is
+// what it uses and every array keeps an address of its own for the instructions' offset fields (as one object
+// of this struct the 22 ANG kernels without a translation wave took 8 bytes more, the size rounded up to the
+// rows' alignment, and the chain's tail formed its lane offsets again per array).
+template <typename Real, int SC, bool STG, bool HELP, bool ANG, bool TW>
+struct StepLds {
+    using Slots = PoseSlots<Real, SC>;
+    static constexpr int kTwOut = HF_VEL + 3;
+    static constexpr int kRows = STG ? kStepBlock * kRowF4 + (ANG ? 3 * kStepBlock : 0) : 1;
+    float4* rows;
+    typename Slots::Real2* tw_q;
+    Real *rs_body, *tw_out, *ang_q_own, *ang_r, *ang_p;
+    float *rs_obs, *ang_y;
+    int *done_cnt, *tw_mark;
+    uint8_t *done_list, *done_b, *tw_flag;
+#ifdef ADRP_RACE_TIMING
+    unsigned long long* tw_time;
+#endif
+
+    __device__ __forceinline__ Slots slots() { return {tw_q, tw_mark}; }
+    __device__ __forceinline__ Real* ang_q() {
+        if constexpr (TW) return tw_out + HF_QUAT * kStepBlock;
+        else return ang_q_own;
+    }
+    __device__ __forceinline__ Q4<Real> ang_q_read(int tl) {
+        Real* const p = ang_q();
+        return {p[tl], p[kStepBlock + tl], p[2 * kStepBlock + tl], p[3 * kStepBlock + tl]};
+    }
+    __device__ __forceinline__ void ang_q_write(int tl, Q4<Real> v) {
+        Real* const p = ang_q();
+        p[tl] = v.x; p[kStepBlock + tl] = v.y; p[2 * kStepBlock + tl] = v.z;
+        p[3 * kStepBlock + tl] = v.w;
+    }
+};
 
 // B == 0: runtime ring length a.B;  SC > 0: compile-time sub-step count (loop fully unrolled);
 // STG: LDS-staged obs rows (needs A == 4, B == 15 and every lane of the block live);
@@ -1066,477 +165,445 @@ __device__ __forceinline__ void stage_row(float4* lds_row, const float o12[12], 
 // caller already read them (pre[0..A-1], the persistent kernel's line mode).
 // FO: the state's field addressing (body_offsets): 1 = 32-bit offsets (the host saw that E fits), 0 = 64-bit
 // indices, 2 = decided here from E (a branch at the loads and at the stores).
-template <typename Real, int PH, int A, int B, int SC, bool STG = false, int CTL = 0, bool HELP = false, int SYS = 0,
-          int FO = 2>
-__device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const HoverConst<Real>& C,
-                                                const float* pre = nullptr) {
-    constexpr int BR = B > 0 ? B : 1;
-    constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
-    constexpr bool DYN = (PH == ADRP_PHYS_DYN);
+// What follows from those:
+// ANG: the obs row's angles are computed by the helper waves from the chain's final quaternion (LDS): pitch
+// and yaw by two more waves, the roll by the reset helper, whose own work ends before barrier A.  The chain's
+// tail holds none of the three float64 atan2-class evaluations and ends at its state stores: the helper waves
+// copy out all eighteen columns of the block (helper_ring, helper_tail).
+// TW: the yaw helper is also the translation wave (PoseSlots)
+// LATE_XY (ANG with unrolled sub-steps, no translation wave): pos.x / pos.y are summed behind barrier A
+// (pyb_chain's vxy)
+template <typename Real_, int PH_, int A_, int B_, int SC_, bool STG_, int CTL_, bool HELP_, int SYS_, int FO_>
+struct StepForm {
+    using Real = Real_;
+    static constexpr int PH = PH_, A = A_, B = B_, SC = SC_, CTL = CTL_, SYS = SYS_, FO = FO_;
+    static constexpr int BR = B > 0 ? B : 1;
+    static constexpr bool STG = STG_, HELP = HELP_;
+    static constexpr bool DRAG = (PH == ADRP_PHYS_PYB_DRAG || PH == ADRP_PHYS_PYB_GND_DRAG_DW);
+    static constexpr bool DYN = (PH == ADRP_PHYS_DYN);
+    static constexpr bool ANG = HELP && angle_helpers<Real>();
+    static constexpr bool TW = ANG && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0;
+    static constexpr bool LATE_XY = ANG && !DYN && SC > 0 && !TW;
+    // the chain wave's share of the block's coalesced copy-out where it has one: every column without a
+    // helper, half of them beside the single fp32 helper (ANG: none, the three helper waves copy out)
+    static constexpr int kChainCols = HELP ? kRowF4 / 2 : kRowF4;
     static_assert(!HELP || STG, "the reset helper wave pairs with the staged (all lanes live) kernel");
-    // ANG: the obs row's angles are computed by the helper waves from the chain's final quaternion (LDS):
-    // pitch and yaw by two more waves, the roll by the reset helper, whose own work ends before barrier A.
-    // The chain's tail holds none of the three float64 atan2-class evaluations
-    constexpr bool ANG = HELP && angle_helpers<Real>();
-    __shared__ Real rs_body[HELP ? kResetFields * kStepBlock : 1];
-    __shared__ float rs_obs[HELP && !ANG ? 12 * kStepBlock : 1];
-    // (ANG: behind the 64 staged rows, the reset obs of the block's envs as three float4 per env, kResetObs)
-    constexpr int kResetObs = kStepBlock * kRowF4;
-    __shared__ float4 rows[STG ? kStepBlock * kRowF4 + (ANG ? 3 * kStepBlock : 0) : 1];
-    // (pose hand-off kernels, POSE below: the four quaternion rows live in tw_out's, which nobody else uses)
-    constexpr bool kPoseQ = ANG && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0 && ADRP_HOVER_TRANS_WAVE != 0 &&
-                            ADRP_HOVER_POSE_HANDOFF != 0;
-    __shared__ Real ang_q_own[ANG && !kPoseQ ? 4 * kStepBlock : 1];
-    __shared__ Real ang_r[ANG ? kStepBlock : 1];
-    __shared__ Real ang_p[ANG ? kStepBlock : 1];
-    __shared__ float ang_y[ANG ? kStepBlock : 1];
-    // the block's coalesced copy-out dealt over its waves: float4 columns [cb(w), cb(w + 1)) of the
-    // rows (the ANG kernels deal the copy-out differently, TROWS below: cb(1) = 0, none for the chain)
-    constexpr int kWaves = HELP ? 1 + help_waves<Real>() : 1;
-    constexpr auto cb = [](int w) { return w == 0 ? 0 : (w >= kWaves ? kRowF4 : (kWaves == 2 ? kRowF4 / 2 : 6 * (w - 1))); };
-    // TROWS (the ANG kernels): the chain wave ends at its state stores.  It decides the tilt truncation from
-    // the quaternion (trunc_from_quat), stages its nine kinematic floats that are not angles, writes one byte
-    // per lane (done_b: the env is done), enters the done lanes into done_list at their rank, the count into
-    // done_cnt, takes the reset state of its done lanes from rs_body and stores the state.  The three helper
-    // waves (192 lanes) put their angle into the staged rows as float32 (row float 3, 4, 5) and copy out all
-    // eighteen columns of the block:
-    //   before barrier C, while the chain is still at work, the fifteen ring columns, which are final at
-    //   barrier A: five float4 per lane (helper_ring);
-    //   behind barrier B the three kinematic columns, one float4 per lane (lane g: column g % 3 of row g / 3),
-    //   for a done env from the reset obs (kResetObs) instead of the staged row; and the staged rows of the
-    //   listed envs, which the reset never touches, as terminal rows, ten rows per pass over lanes 0..179
-    //   (lane g: list entry g / 18, column g % 18) (helper_tail).
-    constexpr bool TROWS = ANG;
-    constexpr int kHelpLanes = 3 * kStepBlock, kRingF4 = kRowF4 - 3;
-    constexpr int kRingPer = kStepBlock * kRingF4 / kHelpLanes;   // ring float4 per helper lane
-    constexpr int kTermRows = kHelpLanes / kRowF4;                // terminal rows per pass
-    static_assert(!TROWS || (kWaves == 4 && kRingPer * kHelpLanes == kStepBlock * kRingF4 && cb(1) == 0),
-                  "copy-out over three helper waves");
-    __shared__ int done_cnt[1];
-    __shared__ uint8_t done_list[TROWS ? kStepBlock : 1];
-    __shared__ uint8_t done_b[TROWS ? kStepBlock : 1];
-    // TW: the translation wave.  With plain PYB and no external force the translational half of a sub-step
-    // (force, |v|, velocity and its clamp, position, plane contact) feeds nothing back into the rotation; all
-    // it takes from there is the thrust axis, which with the link lag is the z axis of the pose TWO sub-steps
-    // back.  Wave 3, the yaw helper, otherwise idle before barrier A, runs that half for the chain's lanes:
-    //   the chain (pyb_chain's hand-off) writes the z axis of each of its poses into slot k of tw_zxy / tw_zz
-    //   (k = 0: cached link basis, 1: pose at entry, s + 2: pose behind sub-step s), then tw_mark[k].  It only
-    //   writes: no load of pos / vel, no wait, no poll before A.  One wave's LDS operations complete in order,
-    //   so the mark is visible after the data.  (LDS keeps whatever the last workgroup on the CU left: wave 3
-    //   clears the marks and waits for the clears to land ahead of a bare s_barrier that the helper waves pass
-    //   at their head and the chain wave ahead of its first slot write: the head barrier.)
-    //   wave 3 loads pos, vel and the action itself, forms the prop force sum as pyb_chain does, and per
-    //   sub-step s polls the mark of its thrust axis and runs pyb_trans_substep; only when a lane is near the
-    //   plane does it also wait for slot s + 2 (the pose behind the sub-step) for the contact test.  It owns the
-    //   contact counter, the reward, `terminated`, the position limits of `truncated` (one flag byte per lane,
-    //   tw_flag) and row floats 0-2 and 6-8, and leaves the final pos / vel in tw_out, indexed as rs_body is:
-    //   the chain takes the six values behind A from there or, for a done lane, from rs_body by one select of
-    //   the base.  Every state store stays on the chain.
-    constexpr bool TW = TROWS && PH == ADRP_PHYS_PYB && CTL == 0 && SC > 0 && ADRP_HOVER_TRANS_WAVE != 0;
-    // Pose hand-off (ADRP_HOVER_POSE_HANDOFF, POSE below): slot k of tw_q takes the pose's quaternion instead, as
-    // two 16-byte halves (the chain holds it anyway, for the next quaternion product), and wave 3 forms the z
-    // axis at each read, thrust axis and contact test alike: col2_fm, the chain's own expression on the chain's
-    // own bits.  tw_zxy / tw_zz are gone.  Slots 0 and 1, the cached link basis and the pose at entry, are state
-    // fields as loaded: wave 3 loads them itself beside pos / vel and needs no mark for them, tw_q holds slots
-    // 2 .. SC + 1 alone, and the final quaternion for the angle helpers goes to the four rows of tw_out that
-    // were unused (ang_q), so that three workgroups still fit the CU's 160 KB as before.  The marks are what they were, one word per slot, never per lane or
-    // per value: a NaN, gimbal-lock or clamped lane is stored and marked like any other.  Nobody waits forever:
-    // wave 3's clear of all kSlots mark words lands before the head barrier and no mark is written ahead of that
-    // barrier; behind it the chain writes every one of its marks without a wait, a poll or a barrier of its own
-    // before A, and wave 3 waits for chain marks alone.  The wait graph is chain -> wave 3, no cycle, and every
-    // polling wave reaches A whatever the data holds.
-    constexpr int kSlots = SC + 2, kTwOut = HF_VEL + 3;
-    constexpr bool POSE = TW && ADRP_HOVER_POSE_HANDOFF != 0;
-    using Real2 = Real __attribute__((ext_vector_type(2)));
-    [[maybe_unused]] __shared__ Real2 tw_q[POSE ? 2 * (kSlots - 2) * kStepBlock : 1];
-    __shared__ Real2 tw_zxy[TW && !POSE ? kSlots * kStepBlock : 1];
-    __shared__ Real tw_zz[TW && !POSE ? kSlots * kStepBlock : 1];
-    __shared__ int tw_mark[TW ? kSlots : 1];
-    __shared__ Real tw_out[TW ? kTwOut * kStepBlock : 1];
-    static_assert(kPoseQ == POSE, "ang_q's home");
-    [[maybe_unused]] Real* const ang_q = POSE ? tw_out + HF_QUAT * kStepBlock : ang_q_own;
-    __shared__ uint8_t tw_flag[TW ? kStepBlock : 1];
-#ifdef ADRP_RACE_TIMING
-    __shared__ unsigned long long tw_time[1];
-#endif
-    // The marks are relaxed workgroup-scope atomics (plain ds_read / ds_write, no s_waitcnt of their own); the
-    // empty asm keeps the compiler from moving the data accesses across them, the LDS keeps a wave's order.
-    [[maybe_unused]] auto slot_wait = [&](int k) {   // one LDS word per poll; the chain wave is co-resident and always arrives
-        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&tw_mark[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0)
-            __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-    };
-    [[maybe_unused]] auto slot_read = [&](int k, int tl) {   // the z axis of the pose in slot k
-        if constexpr (POSE) {
-            const Real2 xy = tw_q[(2 * k - 4) * kStepBlock + tl], zw = tw_q[(2 * k - 3) * kStepBlock + tl];
-            return col2_fm(Q4<Real>{Real(xy.x), Real(xy.y), Real(zw.x), Real(zw.y)});
-        } else {
-            const Real2 xy = tw_zxy[k * kStepBlock + tl];
-            return v3(Real(xy.x), Real(xy.y), tw_zz[k * kStepBlock + tl]);
+    static_assert(!STG || (A == 4 && B == 15), "staged rows: 72-float rows only");
+    using Lds = StepLds<Real, SC, STG, HELP, ANG, TW>;
+};
+
+// ---- pieces that more than one role runs ----
+
+// BaseAviary.reset of a done lane from the reset helper's LDS copy
+template <typename Real>
+__device__ __forceinline__ void take_reset_state(const Real* rs_body, int t, Body<Real>& b, int32_t& sc, int32_t& ep) {
+    Real v[kResetFields];
+#pragma unroll
+    for (int k = 0; k < kResetFields; ++k) v[k] = rs_body[k * kStepBlock + t];
+    b.pos = v3(v[0], v[1], v[2]);
+    b.q = {v[3], v[4], v[5], v[6]};
+    b.ql = b.q;
+    b.vel = v3(v[7], v[8], v[9]);
+    b.w = v3(v[10], v[11], v[12]);
+    b.angv = v3(v[13], v[14], v[15]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
+    sc = 0;
+    ep += 1;
+}
+
+// The ring part of a staged obs row, oldest first; the appended action av is the newest entry (deque.append).
+// Every env appends once per env.step and resets keep the ring, so the head is the same for every env in
+// practice: then the slot -> row position map is scalar and the action simply overwrites the newest position.
+template <int B>
+__device__ __forceinline__ void stage_ring(float4* my, const float (&rg)[B][4], float4 av, int32_t head) {
+    const int hu = __builtin_amdgcn_readfirstlane(head);
+    if (__all(head == hu)) {
+        const int h1 = hu + 1 == B ? 0 : hu + 1;
+#pragma unroll
+        for (int p = 0; p < B; ++p) {
+            const int k = p >= h1 ? p - h1 : p - h1 + B;
+            my[3 + k] = make_float4(rg[p][0], rg[p][1], rg[p][2], rg[p][3]);
         }
-    };
-    [[maybe_unused]] auto slot_write = [&](int k, auto z) {   // the chain wave's hand-off (stores only): z axis or pose
-        const int tl = threadIdx.x;
-        // The chain's head barrier sits here, ahead of its first LDS write and behind its loads and the pre-loop:
-        // the translation wave's lgkmcnt(0) in front of the barrier also covers that wave's kernel-argument
-        // loads, which come in cold (later than the chain's state loads), and by now they have
-        if (k == 0) __builtin_amdgcn_s_barrier();
-        if constexpr (__is_same(decltype(z), Q4<Real>)) {
-            if (k < 2) return;   // (the cached link basis and the pose at entry: wave 3 loads them as the chain does)
-            Real2 xy, zw;
-            xy.x = z.x; xy.y = z.y; zw.x = z.z; zw.y = z.w;
-            tw_q[(2 * k - 4) * kStepBlock + tl] = xy;
-            tw_q[(2 * k - 3) * kStepBlock + tl] = zw;
-        } else {
-            Real2 xy;
-            xy.x = z.x; xy.y = z.y;
-            tw_zxy[k * kStepBlock + tl] = xy;
-            tw_zz[k * kStepBlock + tl] = z.z;
-        }
-        if (k > 0) {   // (slot 0 goes with slot 1)
-            asm volatile("" ::: "memory");
-            __hip_atomic_store(&tw_mark[k], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    };
-    // What a helper lane's copies need that depends on the lane alone, formed (and held in registers) while
-    // the wave waits for barrier A.  Byte offsets within `rows`, which are the byte offsets within the block's
-    // obs rows too: ring[j] of ring float4 g + 192 j (column 3 + n % 15 of row n / 15), kin of the lane's
-    // kinematic float4, fix of the same column of the row's reset obs; flag: the row; sub, tcol: the lane's
-    // list entry and column of a terminal row pass
-    struct TailIdx {
-        uint32_t ring[kRingPer], kin, fix, flag, sub, tcol;
-    };
-    [[maybe_unused]] auto tail_index = [&](int tl, int wv) {
-        TailIdx t;
-        const uint32_t g = uint32_t(wv - 1) * kStepBlock + uint32_t(tl);
+        my[3 + B - 1] = av;
+    } else {
+        const int h1 = head + 1 == B ? 0 : head + 1;
 #pragma unroll
-        for (int j = 0; j < kRingPer; ++j) {
-            const uint32_t n = g + kHelpLanes * uint32_t(j);
-            const uint32_t row = (n * 4370u) >> 16;   // n / 15 for n < 960
-            t.ring[j] = (row * kRowF4 + 3u + (n - kRingF4 * row)) * 16u;
-            asm volatile("" : "+v"(t.ring[j]));
-        }
-        t.flag = (g * 21846u) >> 16;                  // g / 3 for g < 192
-        t.kin = (t.flag * kRowF4 + (g - 3u * t.flag)) * 16u;
-        t.fix = (kResetObs + g) * 16u;
-        t.sub = (g * 3641u) >> 16;                    // g / 18 for g < 192
-        t.tcol = g - kRowF4 * t.sub;
-        asm volatile("" : "+v"(t.kin), "+v"(t.fix), "+v"(t.flag), "+v"(t.sub), "+v"(t.tcol));
-        return t;
-    };
-    [[maybe_unused]] auto helper_ring = [&](const TailIdx& ti) {
-        const char* lds = reinterpret_cast<const char*>(rows);
-        char* dst = reinterpret_cast<char*>(a.obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
-        float4 o[kRingPer];
-#pragma unroll
-        for (int j = 0; j < kRingPer; ++j) o[j] = *reinterpret_cast<const float4*>(lds + ti.ring[j]);
-#pragma unroll
-        for (int j = 0; j < kRingPer; ++j) store_out(reinterpret_cast<float4*>(dst + ti.ring[j]), o[j]);
-    };
-    // A helper lane's work behind barrier B.  The count, the first pass's list entry and, through it, the first
-    // pass's float4 are read ahead of the obs store, needed or not (a list entry past the count is stale: it
-    // is masked to a row of the block and not stored), so that the common single pass adds one predicated
-    // store to the wave's tail and no LDS round trip.
-    [[maybe_unused]] auto helper_tail = [&](const TailIdx& ti) {
-        const int cnt_v = done_cnt[0];
-        const int row0 = done_list[ti.sub] & (kStepBlock - 1);
-        const uint8_t fl = done_b[ti.flag];
-        const char* lds = reinterpret_cast<const char*>(rows);
-        char* dst = reinterpret_cast<char*>(a.obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
-        const float4 o = *reinterpret_cast<const float4*>(lds + (fl ? ti.fix : ti.kin));
-        float4 t0 = rows[row0 * kRowF4 + int(ti.tcol)];
-        hold(t0.x); hold(t0.y); hold(t0.z); hold(t0.w);   // (the read stays here, ahead of the store)
-        store_out(reinterpret_cast<float4*>(dst + ti.kin), o);
-        const int cnt = __builtin_amdgcn_readfirstlane(cnt_v);
-        const int sub = int(ti.sub), c = int(ti.tcol);
-        const bool mine = sub < kTermRows;
-        float4* tb = reinterpret_cast<float4*>(a.tobs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-        if (mine && sub < cnt) tb[row0 * kRowF4 + c] = t0;
-        for (int base = kTermRows; base < cnt && base < kStepBlock; base += kTermRows) {
-            const int n = base + sub;
-            if (mine && n < cnt) {
-                const int row = done_list[n] & (kStepBlock - 1);
-                tb[row * kRowF4 + c] = rows[row * kRowF4 + c];
-            }
-        }
-    };
-    if constexpr (HELP) {
-        if (ANG && threadIdx.x >= 2 * kStepBlock) {   // angle helpers: pitch (wave 2), yaw (wave 3)
-            const int tl = threadIdx.x & (kStepBlock - 1), wv = threadIdx.x / kStepBlock;
-            // TW, wave 3: its loads first, the marks cleared (and the clears landed) before the head barrier
-            [[maybe_unused]] const bool trans = TW && __builtin_amdgcn_readfirstlane(wv) == 3;
-            [[maybe_unused]] V3<Real> tp{}, tv{};
-            [[maybe_unused]] Q4<Real> tq{}, tql{};
-            [[maybe_unused]] float4 tact = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            [[maybe_unused]] float trew = 0.0f;
-            [[maybe_unused]] bool tterm = false;
-            if constexpr (TW) {
-                if (trans) {
-                    const int te_ = int(blockIdx.x) * kStepBlock + tl;
-                    auto fld = [&](int k) {
-                        if constexpr (FO == 1) return field_at(a.f, (uint32_t(k) * uint32_t(a.E) + uint32_t(te_)) * uint32_t(sizeof(Real)));
-                        else return a.f[size_t(k) * a.E + te_];
-                    };
-                    tp = v3(fld(HF_POS + 0), fld(HF_POS + 1), fld(HF_POS + 2));
-                    tv = v3(fld(HF_VEL + 0), fld(HF_VEL + 1), fld(HF_VEL + 2));
-                    if constexpr (POSE) {   // slots 0 and 1 of the hand-off: what the chain loads as b.ql and b.q
-                        tq = {fld(HF_QUAT + 0), fld(HF_QUAT + 1), fld(HF_QUAT + 2), fld(HF_QUAT + 3)};
-                        tql = tq;
-                        if (C.link_lag)
-                            tql = {fld(HF_LINK_QUAT + 0), fld(HF_LINK_QUAT + 1), fld(HF_LINK_QUAT + 2), fld(HF_LINK_QUAT + 3)};
-                    }
-                    tact = reinterpret_cast<const float4*>(a.act)[te_];
-                    if (tl < kSlots) __hip_atomic_store(&tw_mark[tl], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the clears are in LDS
-                }
-                __builtin_amdgcn_s_barrier();   // head: no mark of this launch is written before every clear
-            }
-            AngK ak = ang_consts();   // the lean angle forms' constants, into VGPRs while the wave is idle
-            pin_all(ak);
-            const TailIdx ti = tail_index(tl, wv);
-            if constexpr (TW) {
-                if (trans) {   // the translational half of the eight sub-steps, behind the chain's thrust axes
-                    const bool lag = C.link_lag;
-                    ChainK<Real> K = chain_consts<Real>();
-                    HoverConst<Real> Cp = C;
-                    pin(K.k004); pin(K.c100); pin(K.nn_min);
-                    pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass);
-                    pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
-                    // the prop force sum: pyb_chain's statements (products and sums apart: no contraction)
-                    const float ta[4] = {tact.x, tact.y, tact.z, tact.w};
-                    Real sum_f = 0;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const Real rpm = C.hover_rpm * Real(rpm_gain(ta[i]));
-                        const Real r2 = rpm * rpm;
-                        const Real f = r2 * C.kf;
-                        sum_f += f;
-                    }
-                    bool touched = false;
-                    [[maybe_unused]] bool near = false;
-#pragma unroll
-                    for (int s = 0; s < SC; ++s) {
-                        const int k = lag ? s : s + 1;
-                        V3<Real> zs;
-                        if (POSE && k < 2) {
-                            zs = col2_fm(k == 0 ? tql : tq);
-                        } else {
-                            slot_wait(k > 0 ? k : 1);
-                            zs = slot_read(k, tl);
-                        }
-                        pyb_trans_substep(Cp, tp, tv, zs, sum_f, K);
-                        if (pyb_trans_near_plane(Cp, tp)) {   // (rare) the pose behind this sub-step
-                            slot_wait(s + 2);
-                            touched |= pyb_trans_contact(Cp, tp, tv, slot_read(s + 2, tl));
-                            near = true;
-                        }
-                    }
-                    if (touched && a.contact_count) atomicAdd(a.contact_count, 1);
-#ifdef ADRP_RACE_TIMING
-                    if (tl == 0 && near) atomicAdd(&g_race_phase[24], 1ull);   // waves that took the near-plane path
-#endif
-                    // reward, terminated and the position limits of truncated (HoverAviary.py:68-117): the chain's
-                    // expressions; the chain adds the step limit and the tilt to the flag byte's second bit
-                    const Real dx = C.target[0] - tp.x, dy = C.target[1] - tp.y, dz = C.target[2] - tp.z;
-                    const Real d2 = dx * dx + dy * dy + dz * dz;
-                    const Real r = Real(2) - d2 * d2;
-                    trew = float(r > Real(0) ? r : Real(0));
-                    tterm = d2 < Real(1e-8);
-                    const bool te = tterm;
-                    const bool trp = fabs_(tp.x) > Real(1.5) || fabs_(tp.y) > Real(1.5) || tp.z > Real(2.0);
-                    tw_out[(HF_POS + 0) * kStepBlock + tl] = tp.x; tw_out[(HF_POS + 1) * kStepBlock + tl] = tp.y;
-                    tw_out[(HF_POS + 2) * kStepBlock + tl] = tp.z;
-                    tw_out[(HF_VEL + 0) * kStepBlock + tl] = tv.x; tw_out[(HF_VEL + 1) * kStepBlock + tl] = tv.y;
-                    tw_out[(HF_VEL + 2) * kStepBlock + tl] = tv.z;
-                    tw_flag[tl] = uint8_t((te ? 1 : 0) | (trp ? 2 : 0));
-#ifdef ADRP_RACE_TIMING
-                    if (tl == 0) tw_time[0] = __builtin_amdgcn_s_memtime();   // this wave's arrival at A
-#endif
-                }
-            }
-            __syncthreads();   // A: the chain's final quaternion
-            const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
-            if constexpr (ANG) {   // (this branch is the ANG kernels' alone; fp32 has no lean forms to compile)
-                float* rowf = reinterpret_cast<float*>(rows) + tl * (4 * kRowF4);
-                if constexpr (TW) {
-                    if (trans) {   // what of the translation the chain does not wait for: behind A, where this wave has slack
-                        const int te_ = int(blockIdx.x) * kStepBlock + tl;
-                        a.rew[te_] = trew;
-                        a.term[te_] = tterm;
-                        rowf[0] = float(tp.x); rowf[1] = float(tp.y); rowf[2] = float(tp.z);
-                        rowf[6] = float(tv.x); rowf[7] = float(tv.y); rowf[8] = float(tv.z);
-                    }
-                }
-                if (wv == 2) {
-                    const double p = euler_pitch_lean(q, ak);
-                    ang_p[tl] = p;
-                    rowf[4] = float(p);
-                } else {
-                    const float y = float(euler_yaw_lean(q, ak));
-                    ang_y[tl] = y;
-                    rowf[5] = y;
-                }
-            }
-            if constexpr (TROWS) helper_ring(ti);
-            __syncthreads();   // C: pitch and yaw
-            __syncthreads();   // B: the final rows
-            if constexpr (TROWS) {
-                helper_tail(ti);
-                return;
-            }
-            float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-            for (int k = cb(wv); k < cb(wv + 1); ++k) store_out(dst + tl + kStepBlock * k, rows[tl + kStepBlock * k]);
-            return;
-        }
-        if (threadIdx.x >= kStepBlock) {
-            const int tl = threadIdx.x - kStepBlock;
-            const int he = blockIdx.x * kStepBlock + tl;
-            const int E = a.E;
-            if constexpr (TW) __builtin_amdgcn_s_barrier();   // head (the translation wave's marks are clear)
-            // the action ring: its part of the obs row is independent of the physics, so this
-            // wave loads it, stages it in LDS and appends the action (deque.append)
-            const float4 av = reinterpret_cast<const float4*>(a.act)[he];
-            float rg[BR][4];    // plain floats: float4 struct copies under a select went to scratch
-#pragma unroll
-            for (int p = 0; p < B; ++p) {
-                const float4 v = reinterpret_cast<const float4*>(a.ring)[size_t(p) * E + he];
-                rg[p][0] = v.x; rg[p][1] = v.y; rg[p][2] = v.z; rg[p][3] = v.w;
-            }
-            const int32_t head = a.ist[HI_RING_HEAD * E + he];
-            int32_t hsc = 0, hep = a.ist[HI_EPISODE * E + he];
-            Body<Real> rb;
-            hover_reset_state(a, C, he, rb, hsc, hep);
-            float o[12];
-            hover_obs12(C, rb, o);
-            const Real v[kResetFields] = {rb.pos.x, rb.pos.y, rb.pos.z, rb.q.x, rb.q.y, rb.q.z, rb.q.w,
-                                          rb.vel.x, rb.vel.y, rb.vel.z, rb.w.x, rb.w.y, rb.w.z,
-                                          rb.angv.x, rb.angv.y, rb.angv.z};
-#pragma unroll
-            for (int k = 0; k < kResetFields; ++k) rs_body[k * kStepBlock + tl] = v[k];
-            if constexpr (ANG) {   // as three float4: the helper waves' copy-out takes them whole (helper_tail)
-                rows[kResetObs + 3 * tl + 0] = make_float4(o[0], o[1], o[2], o[3]);
-                rows[kResetObs + 3 * tl + 1] = make_float4(o[4], o[5], o[6], o[7]);
-                rows[kResetObs + 3 * tl + 2] = make_float4(o[8], o[9], o[10], o[11]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) rs_obs[k * kStepBlock + tl] = o[k];
-            }
-            // ring part of the obs row, oldest first; the appended action is the newest entry.
-            // Every env appends once per env.step and resets keep the ring, so the head is the
-            // same for every env in practice: then the slot -> row position map is scalar.
-            float4* my = rows + tl * kRowF4;
-            const int hu = __builtin_amdgcn_readfirstlane(head);
-            if (__all(head == hu)) {
-                const int h1 = hu + 1 == B ? 0 : hu + 1;
-#pragma unroll
-                for (int p = 0; p < B; ++p) {
-                    const int k = p >= h1 ? p - h1 : p - h1 + B;
-                    my[3 + k] = make_float4(rg[p][0], rg[p][1], rg[p][2], rg[p][3]);
-                }
-                my[3 + B - 1] = av;
-            } else {
-                const int h1 = head + 1 == B ? 0 : head + 1;
-#pragma unroll
-                for (int p = 0; p < B; ++p) {
-                    int k = p - h1;
-                    k += k < 0 ? B : 0;
-                    const bool hit = p == head;
-                    my[3 + k] = make_float4(hit ? av.x : rg[p][0], hit ? av.y : rg[p][1], hit ? av.z : rg[p][2],
-                                            hit ? av.w : rg[p][3]);
-                }
-            }
-            reinterpret_cast<float4*>(a.ring)[size_t(head) * E + he] = av;
-            [[maybe_unused]] AngK ak = ang_consts();   // (ANG: pinned behind this wave's reset work, before A)
-            if constexpr (ANG) pin_all(ak);
-            [[maybe_unused]] TailIdx ti{};
-            if constexpr (TROWS) ti = tail_index(tl, 1);
-            __syncthreads();   // A: reset states and ring rows in LDS
-            if constexpr (ANG) {   // this wave is idle from here to the copy-out: it takes the roll
-                const Q4<Real> q = {ang_q[tl], ang_q[kStepBlock + tl], ang_q[2 * kStepBlock + tl], ang_q[3 * kStepBlock + tl]};
-                const double roll = euler_roll_lean(q, ak);
-                ang_r[tl] = roll;
-                reinterpret_cast<float*>(rows)[tl * (4 * kRowF4) + 3] = float(roll);
-                if constexpr (TROWS) helper_ring(ti);
-                __syncthreads();   // C
-            }
-            __syncthreads();   // B: the chain wave's kinematic parts and done marks
-            if constexpr (TROWS) {
-                helper_tail(ti);
-                return;
-            }
-            // this wave's part of the block's coalesced copy-out
-            float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-#pragma unroll
-            for (int k = cb(1); k < cb(2); ++k) store_out(dst + tl + kStepBlock * k, rows[tl + kStepBlock * k]);
-            return;
+        for (int p = 0; p < B; ++p) {
+            int k = p - h1;
+            k += k < 0 ? B : 0;
+            const bool hit = p == head;
+            my[3 + k] = make_float4(hit ? av.x : rg[p][0], hit ? av.y : rg[p][1], hit ? av.z : rg[p][2],
+                                    hit ? av.w : rg[p][3]);
         }
     }
+}
+
+// reward, terminated and the position limits of truncated from a position (HoverAviary.py:68-117)
+struct PosFlags {
+    float rew;
+    bool term, out;
+};
+template <typename Real>
+__device__ __forceinline__ PosFlags hover_pos_flags(const HoverConst<Real>& C, V3<Real> pos) {
+    const Real dx = C.target[0] - pos.x, dy = C.target[1] - pos.y, dz = C.target[2] - pos.z;
+    const Real d2 = dx * dx + dy * dy + dz * dz;
+    const Real r = Real(2) - d2 * d2;
+    PosFlags f;
+    f.rew = float(r > Real(0) ? r : Real(0));
+    f.term = d2 < Real(1e-8);   // |target - pos| < 1e-4
+    f.out = fabs_(pos.x) > Real(1.5) || fabs_(pos.y) > Real(1.5) || pos.z > Real(2.0);
+    return f;
+}
+
+// ---- the ANG kernels' copy-out over the three helper waves (192 lanes) ----
+//   before barrier C, while the chain is still at work, the fifteen ring columns, which are final at
+//   barrier A: five float4 per lane (helper_ring);
+//   behind barrier B the three kinematic columns, one float4 per lane (lane g: column g % 3 of row g / 3),
+//   for a done env from the reset obs (kResetObs) instead of the staged row; and the staged rows of the
+//   listed envs, which the reset never touches, as terminal rows, ten rows per pass over lanes 0..179
+//   (lane g: list entry g / 18, column g % 18) (helper_tail).
+constexpr int kHelpLanes = 3 * kStepBlock, kRingF4 = kRowF4 - 3;
+constexpr int kRingPer = kStepBlock * kRingF4 / kHelpLanes;   // ring float4 per helper lane
+constexpr int kTermRows = kHelpLanes / kRowF4;                // terminal rows per pass
+static_assert(kRingPer * kHelpLanes == kStepBlock * kRingF4, "copy-out over three helper waves");
+// What a helper lane's copies need that depends on the lane alone, formed (and held in registers) while
+// the wave waits for barrier A.  Byte offsets within `rows`, which are the byte offsets within the block's
+// obs rows too: ring[j] of ring float4 g + 192 j (column 3 + n % 15 of row n / 15), kin of the lane's
+// kinematic float4, fix of the same column of the row's reset obs; flag: the row; sub, tcol: the lane's
+// list entry and column of a terminal row pass
+struct TailIdx {
+    uint32_t ring[kRingPer], kin, fix, flag, sub, tcol;
+};
+__device__ __forceinline__ TailIdx tail_index(int tl, int wv) {
+    TailIdx t;
+    const uint32_t g = uint32_t(wv - 1) * kStepBlock + uint32_t(tl);
+#pragma unroll
+    for (int j = 0; j < kRingPer; ++j) {
+        const uint32_t n = g + kHelpLanes * uint32_t(j);
+        const uint32_t row = (n * 4370u) >> 16;   // n / 15 for n < 960
+        t.ring[j] = (row * kRowF4 + 3u + (n - kRingF4 * row)) * 16u;
+        asm volatile("" : "+v"(t.ring[j]));
+    }
+    t.flag = (g * 21846u) >> 16;                  // g / 3 for g < 192
+    t.kin = (t.flag * kRowF4 + (g - 3u * t.flag)) * 16u;
+    t.fix = (kResetObs + g) * 16u;
+    t.sub = (g * 3641u) >> 16;                    // g / 18 for g < 192
+    t.tcol = g - kRowF4 * t.sub;
+    asm volatile("" : "+v"(t.kin), "+v"(t.fix), "+v"(t.flag), "+v"(t.sub), "+v"(t.tcol));
+    return t;
+}
+__device__ __forceinline__ void helper_ring(const float4* rows, float* obs, const TailIdx& ti) {
+    const char* lds = reinterpret_cast<const char*>(rows);
+    char* dst = reinterpret_cast<char*>(obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
+    float4 o[kRingPer];
+#pragma unroll
+    for (int j = 0; j < kRingPer; ++j) o[j] = *reinterpret_cast<const float4*>(lds + ti.ring[j]);
+#pragma unroll
+    for (int j = 0; j < kRingPer; ++j) store_out(reinterpret_cast<float4*>(dst + ti.ring[j]), o[j]);
+}
+// A helper lane's work behind barrier B.  The count, the first pass's list entry and, through it, the first
+// pass's float4 are read ahead of the obs store, needed or not (a list entry past the count is stale: it
+// is masked to a row of the block and not stored), so that the common single pass adds one predicated
+// store to the wave's tail and no LDS round trip.
+template <typename Real, typename Lds>
+__device__ __forceinline__ void helper_tail(const HoverArgs<Real>& a, Lds& l, const TailIdx& ti) {
+    const int cnt_v = l.done_cnt[0];
+    const int row0 = l.done_list[ti.sub] & (kStepBlock - 1);
+    const uint8_t fl = l.done_b[ti.flag];
+    const char* lds = reinterpret_cast<const char*>(l.rows);
+    char* dst = reinterpret_cast<char*>(a.obs) + size_t(blockIdx.x) * (kStepBlock * kRowF4 * sizeof(float4));
+    const float4 o = *reinterpret_cast<const float4*>(lds + (fl ? ti.fix : ti.kin));
+    float4 t0 = l.rows[row0 * kRowF4 + int(ti.tcol)];
+    hold(t0.x); hold(t0.y); hold(t0.z); hold(t0.w);   // (the read stays here, ahead of the store)
+    store_out(reinterpret_cast<float4*>(dst + ti.kin), o);
+    const int cnt = __builtin_amdgcn_readfirstlane(cnt_v);
+    const int sub = int(ti.sub), c = int(ti.tcol);
+    const bool mine = sub < kTermRows;
+    float4* tb = reinterpret_cast<float4*>(a.tobs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+    if (mine && sub < cnt) tb[row0 * kRowF4 + c] = t0;
+    for (int base = kTermRows; base < cnt && base < kStepBlock; base += kTermRows) {
+        const int n = base + sub;
+        if (mine && n < cnt) {
+            const int row = l.done_list[n] & (kStepBlock - 1);
+            tb[row * kRowF4 + c] = l.rows[row * kRowF4 + c];
+        }
+    }
+}
+
+// ---- role: the translation wave (wave 3 of a TW kernel; PoseSlots has the protocol) ----
+// It loads pos, vel, the two quaternions of slots 0 and 1 and the action itself, forms the prop force sum
+// as pyb_chain does, and per sub-step s polls the mark of its thrust axis and runs pyb_trans_substep; only
+// when a lane is near the plane does it also wait for slot s + 2 (the pose behind the sub-step) for the
+// contact test.  It owns the contact counter, the reward, `terminated`, the position limits of `truncated`
+// (tw_flag) and row floats 0-2 and 6-8, and leaves the final pos / vel in tw_out.  Every state store stays
+// on the chain.
+template <typename Real>
+struct TransWave {
+    V3<Real> pos{}, vel{};
+    Q4<Real> q{}, ql{};   // slots 1 and 0 of the hand-off: what the chain loads as b.q and b.ql
+    float4 act = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float rew = 0.0f;
+    bool term = false;
+};
+// its loads first, the marks cleared (and the clears landed) before the head barrier
+template <class F>
+__device__ __forceinline__ void trans_wave_load(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                typename F::Lds& l, int tl, TransWave<typename F::Real>& t) {
+    using Real = typename F::Real;
+    const int te_ = int(blockIdx.x) * kStepBlock + tl;
+    auto fld = [&](int k) {
+        if constexpr (F::FO == 1) return field_at(a.f, (uint32_t(k) * uint32_t(a.E) + uint32_t(te_)) * uint32_t(sizeof(Real)));
+        else return a.f[size_t(k) * a.E + te_];
+    };
+    t.pos = v3(fld(HF_POS + 0), fld(HF_POS + 1), fld(HF_POS + 2));
+    t.vel = v3(fld(HF_VEL + 0), fld(HF_VEL + 1), fld(HF_VEL + 2));
+    t.q = {fld(HF_QUAT + 0), fld(HF_QUAT + 1), fld(HF_QUAT + 2), fld(HF_QUAT + 3)};
+    t.ql = t.q;
+    if (C.link_lag)
+        t.ql = {fld(HF_LINK_QUAT + 0), fld(HF_LINK_QUAT + 1), fld(HF_LINK_QUAT + 2), fld(HF_LINK_QUAT + 3)};
+    t.act = reinterpret_cast<const float4*>(a.act)[te_];
+    l.slots().clear(tl);
+}
+// the translational half of the sub-steps, behind the chain's poses; reward and flags
+template <class F>
+__device__ __forceinline__ void hover_trans_wave(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                 typename F::Lds& l, int tl, TransWave<typename F::Real>& t) {
+    using Real = typename F::Real;
+    const auto slots = l.slots();
+    const bool lag = C.link_lag;
+    ChainK<Real> K = chain_consts<Real>();
+    HoverConst<Real> Cp = C;
+    pin(K.k004); pin(K.c100); pin(K.nn_min);
+    pin(Cp.dt); pin(Cp.mass); pin(Cp.gravity); pin(Cp.inv_mass);
+    pin(Cp.coll_hh); pin(Cp.coll_r); pin(Cp.coll_zoff);
+    const float ta[4] = {t.act.x, t.act.y, t.act.z, t.act.w};
+    Real rpm[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rpm[i] = C.hover_rpm * Real(rpm_gain(ta[i]));
+    const Real sum_f = prop_sums(C, rpm).sum_f;
+    bool touched = false;
+    [[maybe_unused]] bool near = false;
+#pragma unroll
+    for (int s = 0; s < F::SC; ++s) {
+        const int k = lag ? s : s + 1;
+        V3<Real> zs;
+        if (k < 2) {
+            zs = col2_fm(k == 0 ? t.ql : t.q);
+        } else {
+            slots.wait(k);
+            zs = slots.zaxis(k, tl);
+        }
+        pyb_trans_substep(Cp, t.pos, t.vel, zs, sum_f, K);
+        if (pyb_trans_near_plane(Cp, t.pos)) {   // (rare) the pose behind this sub-step
+            slots.wait(s + 2);
+            touched |= pyb_trans_contact(Cp, t.pos, t.vel, slots.zaxis(s + 2, tl));
+            near = true;
+        }
+    }
+    if (touched && a.contact_count) atomicAdd(a.contact_count, 1);
+#ifdef ADRP_RACE_TIMING
+    if (tl == 0 && near) atomicAdd(&g_race_phase[24], 1ull);   // waves that took the near-plane path
+#endif
+    // the chain adds the step limit and the tilt to the flag byte's second bit
+    const PosFlags pf = hover_pos_flags(C, t.pos);
+    t.rew = pf.rew;
+    t.term = pf.term;
+    l.tw_out[(HF_POS + 0) * kStepBlock + tl] = t.pos.x; l.tw_out[(HF_POS + 1) * kStepBlock + tl] = t.pos.y;
+    l.tw_out[(HF_POS + 2) * kStepBlock + tl] = t.pos.z;
+    l.tw_out[(HF_VEL + 0) * kStepBlock + tl] = t.vel.x; l.tw_out[(HF_VEL + 1) * kStepBlock + tl] = t.vel.y;
+    l.tw_out[(HF_VEL + 2) * kStepBlock + tl] = t.vel.z;
+    l.tw_flag[tl] = uint8_t((pf.term ? 1 : 0) | (pf.out ? 2 : 0));
+#ifdef ADRP_RACE_TIMING
+    if (tl == 0) l.tw_time[0] = __builtin_amdgcn_s_memtime();   // this wave's arrival at A
+#endif
+}
+// what of the translation the chain does not wait for: behind A, where this wave has slack
+template <typename Real>
+__device__ __forceinline__ void trans_wave_rows(const HoverArgs<Real>& a, float* rowf, int tl, const TransWave<Real>& t) {
+    const int te_ = int(blockIdx.x) * kStepBlock + tl;
+    a.rew[te_] = t.rew;
+    a.term[te_] = t.term;
+    rowf[0] = float(t.pos.x); rowf[1] = float(t.pos.y); rowf[2] = float(t.pos.z);
+    rowf[6] = float(t.vel.x); rowf[7] = float(t.vel.y); rowf[8] = float(t.vel.z);
+}
+
+// ---- role: the angle helpers (ANG kernels): pitch (wave 2), yaw (wave 3, in TW kernels behind the translation) ----
+template <class F>
+__device__ __forceinline__ void hover_angle_helper(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                   typename F::Lds& l) {
+    using Real = typename F::Real;
+    const int tl = threadIdx.x & (kStepBlock - 1), wv = threadIdx.x / kStepBlock;
+    [[maybe_unused]] const bool trans = F::TW && __builtin_amdgcn_readfirstlane(wv) == 3;
+    [[maybe_unused]] TransWave<Real> tw;
+    if constexpr (F::TW) {
+        if (trans) trans_wave_load<F>(a, C, l, tl, tw);
+        F::Lds::Slots::head();
+    }
+    AngK ak = ang_consts();   // the lean angle forms' constants, into VGPRs while the wave is idle
+    pin_all(ak);
+    const TailIdx ti = tail_index(tl, wv);
+    if constexpr (F::TW) {
+        if (trans) hover_trans_wave<F>(a, C, l, tl, tw);
+    }
+    __syncthreads();   // A: the chain's final quaternion
+    const Q4<Real> q = l.ang_q_read(tl);
+    float* rowf = reinterpret_cast<float*>(l.rows) + tl * (4 * kRowF4);
+    if constexpr (F::TW) {
+        if (trans) trans_wave_rows(a, rowf, tl, tw);
+    }
+    if (wv == 2) {
+        const double p = euler_pitch_lean(q, ak);
+        l.ang_p[tl] = p;
+        rowf[4] = float(p);
+    } else {
+        const float y = float(euler_yaw_lean(q, ak));
+        l.ang_y[tl] = y;
+        rowf[5] = y;
+    }
+    helper_ring(l.rows, a.obs, ti);
+    __syncthreads();   // C: pitch and yaw
+    __syncthreads();   // B: the final rows
+    helper_tail(a, l, ti);
+}
+
+// ---- role: the reset-and-ring helper (wave 1 of a HELP kernel) ----
+// The action ring's part of the obs row is independent of the physics, so this wave loads it, stages it in LDS
+// and appends the action; it draws the next-episode state of every env of the block and its obs into LDS; and
+// in ANG kernels, idle from barrier A to the copy-out, it takes the roll.
+template <class F>
+__device__ __forceinline__ void hover_reset_helper(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                   typename F::Lds& l) {
+    using Real = typename F::Real;
+    constexpr int B = F::B;
+    const int tl = threadIdx.x - kStepBlock;
+    const int he = blockIdx.x * kStepBlock + tl;
     const int E = a.E;
-    // SPLIT (a step of ONE env, BASELINE config 1: launched or persistent): every lane of the wave runs
-    // env 0 (the same inputs, the same code: the duplicate stores write the same values) so that three
-    // lanes can take the three obs angles at once; contacts are counted by lane 0 alone
-    const bool split = ADRP_PERSIST_SPLIT && !STG && !HELP && E == 1;
-    const int e = split ? 0 : int(blockIdx.x) * kStepBlock + int(threadIdx.x);
-    const int D = B > 0 ? 12 + B * A : a.D;
-    if (e >= E) return;
-    RACE_MARK(t0);
-    // ---- issue every load up front: state (the chain's first operands) and ints, action, the whole ring ----
-    // one 32-bit byte offset per field on the uniform base (body_offsets), kept for the stores
-    const bool fit = FO == 2 ? field_offsets_fit<Real>(E) : FO == 1;
-    const bool lag = C.link_lag && !DYN;
-    // (the offsets are formed on both sides of the branch, so that they are no merged values at the stores)
-    const BodyOffs<Real> fo = body_offsets<Real>(E, e, lag, DRAG, DYN);
+    if constexpr (F::TW) F::Lds::Slots::head();   // (the translation wave's marks are clear)
+    const float4 av = reinterpret_cast<const float4*>(a.act)[he];
+    float rg[B][4];    // plain floats: float4 struct copies under a select went to scratch
+#pragma unroll
+    for (int p = 0; p < B; ++p) {
+        const float4 v = reinterpret_cast<const float4*>(a.ring)[size_t(p) * E + he];
+        rg[p][0] = v.x; rg[p][1] = v.y; rg[p][2] = v.z; rg[p][3] = v.w;
+    }
+    const int32_t head = a.ist[HI_RING_HEAD * E + he];
+    int32_t hsc = 0, hep = a.ist[HI_EPISODE * E + he];
+    Body<Real> rb;
+    hover_reset_state(a, C, he, rb, hsc, hep);
+    float o[12];
+    hover_obs12(C, rb, o);
+    const Real v[kResetFields] = {rb.pos.x, rb.pos.y, rb.pos.z, rb.q.x, rb.q.y, rb.q.z, rb.q.w,
+                                  rb.vel.x, rb.vel.y, rb.vel.z, rb.w.x, rb.w.y, rb.w.z,
+                                  rb.angv.x, rb.angv.y, rb.angv.z};
+#pragma unroll
+    for (int k = 0; k < kResetFields; ++k) l.rs_body[k * kStepBlock + tl] = v[k];
+    if constexpr (F::ANG) {   // as three float4: the helper waves' copy-out takes them whole (helper_tail)
+        l.rows[kResetObs + 3 * tl + 0] = make_float4(o[0], o[1], o[2], o[3]);
+        l.rows[kResetObs + 3 * tl + 1] = make_float4(o[4], o[5], o[6], o[7]);
+        l.rows[kResetObs + 3 * tl + 2] = make_float4(o[8], o[9], o[10], o[11]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) l.rs_obs[k * kStepBlock + tl] = o[k];
+    }
+    stage_ring<B>(l.rows + tl * kRowF4, rg, av, head);
+    reinterpret_cast<float4*>(a.ring)[size_t(head) * E + he] = av;
+    if constexpr (F::ANG) {
+        AngK ak = ang_consts();   // (pinned behind this wave's reset work, before A)
+        pin_all(ak);
+        const TailIdx ti = tail_index(tl, 1);
+        __syncthreads();   // A: reset states and ring rows in LDS; the chain's final quaternion
+        const double roll = euler_roll_lean(l.ang_q_read(tl), ak);
+        l.ang_r[tl] = roll;
+        reinterpret_cast<float*>(l.rows)[tl * (4 * kRowF4) + 3] = float(roll);
+        helper_ring(l.rows, a.obs, ti);
+        __syncthreads();   // C: the roll
+        __syncthreads();   // B: the chain wave's done marks
+        helper_tail(a, l, ti);
+    } else {
+        __syncthreads();   // A: reset states and ring rows in LDS
+        __syncthreads();   // B: the chain wave's kinematic parts
+        // this wave's part of the block's coalesced copy-out
+        float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+#pragma unroll
+        for (int k = F::kChainCols; k < kRowF4; ++k) store_out(dst + tl + kStepBlock * k, l.rows[tl + kStepBlock * k]);
+    }
+}
+
+// ---- role: the chain wave; also the whole step of the kernels without helpers and of the persistent kernel ----
+// one lane's env through the step: where its state lies, the state, the action and (without a helper) the ring
+template <class F>
+struct ChainLane {
+    using Real = typename F::Real;
+    int e, D;
+    bool split, lag, fit;
+    BodyOffs<Real> fo;    // one 32-bit byte offset per field on the uniform base (body_offsets), kept for the stores
     uint32_t io[HI_N];
-    field_run(uint32_t(e) * 4u, uint32_t(E) * 4u, 0, HI_N, io);
     Body<Real> b;
-    int32_t sc, ep, head_ld;
-    if (fit) {
-        load_body_at<Real>(a.f, fo, b, lag, DRAG, DYN, !TW);
-        sc = field_at(a.ist, io[HI_STEP]); ep = field_at(a.ist, io[HI_EPISODE]); head_ld = field_at(a.ist, io[HI_RING_HEAD]);
+    int32_t sc, ep, head, head1;
+    float act[F::A];
+    float ring[F::BR][F::A];
+};
+// ---- issue every load up front: state (the chain's first operands) and ints, action, the whole ring ----
+template <class F>
+__device__ __forceinline__ void chain_loads(const HoverArgs<typename F::Real>& a, const float* pre, ChainLane<F>& L) {
+    using Real = typename F::Real;
+    constexpr int A = F::A, B = F::B;
+    const int E = a.E, e = L.e;
+    // (the offsets are formed on both sides of the branch, so that they are no merged values at the stores)
+    L.fo = body_offsets<Real>(E, e, L.lag, F::DRAG, F::DYN);
+    field_run(uint32_t(e) * 4u, uint32_t(E) * 4u, 0, HI_N, L.io);
+    int32_t head_ld;
+    if (L.fit) {
+        load_body_at<Real>(a.f, L.fo, L.b, L.lag, F::DRAG, F::DYN, !F::TW);
+        L.sc = field_at(a.ist, L.io[HI_STEP]); L.ep = field_at(a.ist, L.io[HI_EPISODE]); head_ld = field_at(a.ist, L.io[HI_RING_HEAD]);
         field_form_end();
     } else {
-        load_body(a, e, b, lag, DRAG, DYN);
-        sc = a.ist[HI_STEP * E + e]; ep = a.ist[HI_EPISODE * E + e]; head_ld = a.ist[HI_RING_HEAD * E + e];
-        if constexpr (TW) b.pos = b.vel = v3(Real(0), Real(0), Real(0));   // (the translation wave's: these loads are dead)
+        load_body(a, e, L.b, L.lag, F::DRAG, F::DYN);
+        L.sc = a.ist[HI_STEP * E + e]; L.ep = a.ist[HI_EPISODE * E + e]; head_ld = a.ist[HI_RING_HEAD * E + e];
+        if constexpr (F::TW) L.b.pos = L.b.vel = v3(Real(0), Real(0), Real(0));   // (the translation wave's: these loads are dead)
     }
-    const int32_t head = head_ld;
-    float act[A];
-    if constexpr (SYS == 2) {
+    L.head = head_ld;
+    if constexpr (F::SYS == 2) {
 #pragma unroll
-        for (int j = 0; j < A; ++j) act[j] = pre[j];
-    } else if constexpr (SYS == 1) {
+        for (int j = 0; j < A; ++j) L.act[j] = pre[j];
+    } else if constexpr (F::SYS == 1) {
         uint32_t* sa = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(a.act)) + size_t(e) * A;
 #pragma unroll
         for (int j = 0; j < A; ++j)
-            act[j] = __uint_as_float(__hip_atomic_load(sa + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+            L.act[j] = __uint_as_float(__hip_atomic_load(sa + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
     } else if constexpr (A == 4) {
         const float4 v = reinterpret_cast<const float4*>(a.act)[e];
-        act[0] = v.x; act[1] = v.y; act[2] = v.z; act[3] = v.w;
+        L.act[0] = v.x; L.act[1] = v.y; L.act[2] = v.z; L.act[3] = v.w;
     } else {
 #pragma unroll
-        for (int j = 0; j < A; ++j) act[j] = a.act[e * A + j];
+        for (int j = 0; j < A; ++j) L.act[j] = a.act[e * A + j];
     }
-    float ring[BR][A];
 #pragma unroll
-    for (int p = 0; p < (HELP ? 0 : B); ++p) {   // (no-op for B == 0; HELP: the helper wave's job)
+    for (int p = 0; p < (F::HELP ? 0 : B); ++p) {   // (no-op for B == 0; HELP: the helper wave's job)
         if constexpr (A == 4) {
             const float4 v = reinterpret_cast<const float4*>(a.ring)[size_t(p) * E + e];
-            ring[p][0] = v.x; ring[p][1] = v.y; ring[p][2] = v.z; ring[p][3] = v.w;
+            L.ring[p][0] = v.x; L.ring[p][1] = v.y; L.ring[p][2] = v.z; L.ring[p][3] = v.w;
         } else {
 #pragma unroll
-            for (int j = 0; j < A; ++j) ring[p][j] = a.ring[(size_t(p) * E + e) * A + j];
+            for (int j = 0; j < A; ++j) L.ring[p][j] = a.ring[(size_t(p) * E + e) * A + j];
         }
     }
-    // ---- _preprocessAction: RPM = HOVER_RPM * (1 + 0.05 a), the gain in float32 (NEP 50),
-    //      or the DSLPIDControl output for the PID action types ----
-    Real rpm[4];
+}
+// ---- _preprocessAction: RPM = HOVER_RPM * (1 + 0.05 a), the gain in float32 (NEP 50),
+//      or the DSLPIDControl output for the PID action types ----
+template <class F>
+__device__ __forceinline__ void chain_rpm(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                          const ChainLane<F>& L, typename F::Real rpm[4]) {
+    using Real = typename F::Real;
+    constexpr int A = F::A, CTL = F::CTL;
     if constexpr (CTL != 0) {
         static_assert(A == (CTL == ADRP_ACT_PID ? 3 : CTL == ADRP_ACT_VEL ? 4 : 1), "PID action width");
+        const int E = a.E, e = L.e;
         Real ctl[HF_NPID];
         uint32_t po[HF_PID + HF_NPID];
         field_run(uint32_t(e) * uint32_t(sizeof(Real)), uint32_t(E) * uint32_t(sizeof(Real)), HF_PID, HF_NPID, po);
-        if (fit) {
+        if (L.fit) {
 #pragma unroll
             for (int k = 0; k < HF_NPID; ++k) ctl[k] = field_at(a.f, po[HF_PID + k]);
             field_form_end();
@@ -1544,8 +611,8 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
 #pragma unroll
             for (int k = 0; k < HF_NPID; ++k) ctl[k] = a.f[(HF_PID + k) * E + e];
         }
-        dslpid_rpm<Real, CTL>(C, b, act, ctl, rpm);
-        if (fit) {
+        dslpid_rpm<Real, CTL>(C, L.b, L.act, ctl, rpm);
+        if (L.fit) {
 #pragma unroll
             for (int k = 0; k < HF_NPID; ++k) field_last(a.f, po[HF_PID + k]) = ctl[k];
             field_form_end();
@@ -1555,13 +622,202 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rpm[i] = C.hover_rpm * Real(rpm_gain(act[A == 1 ? 0 : i]));
+        for (int i = 0; i < 4; ++i) rpm[i] = C.hover_rpm * Real(rpm_gain(L.act[A == 1 ? 0 : i]));
     }
+}
+// the state and the ints leave through the offsets of the loads
+template <class F>
+__device__ __forceinline__ void chain_store_state(const HoverArgs<typename F::Real>& a, ChainLane<F>& L) {
+    using Real = typename F::Real;
+    const int E = a.E, e = L.e;
+    if (L.fit) {
+        store_body_at<Real>(a.f, L.fo, L.b, L.lag, F::DRAG, F::DYN);
+        field_last(a.ist, L.io[HI_STEP]) = L.sc;
+        field_last(a.ist, L.io[HI_EPISODE]) = L.ep;
+        field_last(a.ist, L.io[HI_RING_HEAD]) = L.head1;
+        field_form_end();
+    } else {
+        store_body(a, e, L.b, L.lag, F::DRAG, F::DYN);
+        a.ist[HI_STEP * E + e] = L.sc;
+        a.ist[HI_EPISODE * E + e] = L.ep;
+        a.ist[HI_RING_HEAD * E + e] = L.head1;
+    }
+}
+// ANG, behind the final quaternion: barrier A, and the chain's part of the obs row.
+// While the three helper waves take one angle each, the chain does what only it can: ω back to the world
+// frame (deferred by pyb_chain), the conversions and, in the caller, the reward and the angle-free truncation
+// tests.  (hold: arithmetic carries no order against a barrier, and the compiler had placed most of this
+// before A and the rest after C, leaving the chain to wait at C with nothing to do; what the work starts from
+// is taken behind A here, and what it gives is finished before C in the caller.)
+template <class F>
+__device__ __forceinline__ void chain_row_behind_A(const HoverConst<typename F::Real>& C, typename F::Lds& l, Body<typename F::Real>& b,
+                                                   V3<typename F::Real>& wbf, typename F::Real* vxy, float o12[12]) {
+    using Real = typename F::Real;
+    constexpr bool TW = F::TW;
+    l.ang_q_write(threadIdx.x, b.q);
+#ifdef ADRP_RACE_TIMING
+    [[maybe_unused]] const uint64_t t_a = __builtin_amdgcn_s_memtime();   // the chain's arrival at A
+#endif
+    __syncthreads();   // A: the quaternion out; the reset helper's states and ring rows in
+#ifdef ADRP_RACE_TIMING
+    if constexpr (TW) {   // [20] / [21]: cycles the translation wave arrived at A before / behind the chain
+        if (threadIdx.x == 0) {
+            const uint64_t t_w = l.tw_time[0];
+            atomicAdd(&g_race_phase[t_a >= t_w ? 20 : 21], (unsigned long long)(t_a >= t_w ? t_a - t_w : t_w - t_a));
+        }
+    }
+#endif
+    if constexpr (TW) {   // the translation wave's final pos / vel, read while the chain has arithmetic to do
+        const Real* src = l.tw_out + threadIdx.x;
+        b.pos = v3(src[(HF_POS + 0) * kStepBlock], src[(HF_POS + 1) * kStepBlock], src[(HF_POS + 2) * kStepBlock]);
+        b.vel = v3(src[(HF_VEL + 0) * kStepBlock], src[(HF_VEL + 1) * kStepBlock], src[(HF_VEL + 2) * kStepBlock]);
+    }
+    hold(b.q.x); hold(b.q.y); hold(b.q.z); hold(b.q.w);
+    hold(wbf.x); hold(wbf.y); hold(wbf.z);
+    if constexpr (!TW) { hold(b.pos.x); hold(b.pos.y); hold(b.pos.z); }
+    if constexpr (F::LATE_XY) {   // the horizontal position sums of the sub-steps, deferred to here
+#pragma unroll
+        for (int k = 0; k < 2 * F::SC; ++k) hold(vxy[k]);
+#pragma unroll
+        for (int s = 0; s < F::SC; ++s) {
+            b.pos.x = fmx(C.dt, vxy[2 * s], b.pos.x);
+            b.pos.y = fmx(C.dt, vxy[2 * s + 1], b.pos.y);
+        }
+    }
+    if constexpr (!TW) { hold(b.vel.x); hold(b.vel.y); hold(b.vel.z); }
+    if constexpr (!F::DYN) b.w = mul(rot_fm(b.q), wbf);
+    const V3<Real> w = C.physics == ADRP_PHYS_DYN ? b.angv : b.w;   // hover_obs12's row, the angles are the helpers'
+    if constexpr (!TW) {   // (TW: row floats 0-2 and 6-8 are the translation wave's)
+        o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z);
+        o12[6] = float(b.vel.x); o12[7] = float(b.vel.y); o12[8] = float(b.vel.z);
+    }
+    o12[9] = float(w.x);     o12[10] = float(w.y);    o12[11] = float(w.z);
+}
+// The chain's end in ANG kernels: its nine floats of the row that are not angles (the helper waves write
+// floats 3, 4, 5; TW: three, the translation wave has the other six), one byte per lane (done_b: the env is
+// done), the done lanes into done_list at their rank and the count into done_cnt for the helper waves' tail,
+// the reset state of its done lanes from rs_body, the state stores, barriers C and B.
+template <class F>
+__device__ __forceinline__ void chain_end_helpers(const HoverArgs<typename F::Real>& a, typename F::Lds& l, ChainLane<F>& L,
+                                                  const float o12[12], bool done, bool slow, [[maybe_unused]] uint64_t& t4) {
+    float4* my = l.rows + threadIdx.x * kRowF4;
+    float* mf = reinterpret_cast<float*>(my);
+    if constexpr (F::TW) {
+        mf[9] = o12[9]; mf[10] = o12[10]; mf[11] = o12[11];
+    } else {
+        mf[0] = o12[0]; mf[1] = o12[1]; mf[2] = o12[2];
+        mf[6] = o12[6]; mf[7] = o12[7];
+        my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+    }
+    const unsigned long long done_mask = __ballot(done);
+    l.done_b[threadIdx.x] = done;
+    l.done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;   // (every lane writes the same word)
+    if (done) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(uint32_t(done_mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(done_mask), 0u));
+        l.done_list[rank] = uint8_t(threadIdx.x);
+        take_reset_state(l.rs_body, threadIdx.x, L.b, L.sc, L.ep);
+    }
+    RACE_SET(t4);
+    chain_store_state(a, L);
+    if (!slow) __syncthreads();   // C (the unsure wave passed it above)
+    __syncthreads();              // B: the helper waves copy out
+}
+// The chain's end in the other staged kernels.  The obs row is assembled in LDS (18 float4 per lane, no
+// padding: the copy-out reads contiguous float4s at immediate offsets) and leaves as one coalesced block.
+template <class F>
+__device__ __forceinline__ void chain_end_staged(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                 typename F::Lds& l, ChainLane<F>& L, float o12[12], bool done,
+                                                 [[maybe_unused]] uint64_t& t4) {
+    float4* my = l.rows + threadIdx.x * kRowF4;
+    // (HELP: the ring part of the row is staged by the helper wave)
+    if constexpr (!F::HELP) stage_ring<F::B>(my, L.ring, make_float4(L.act[0], L.act[1], L.act[2], L.act[3]), L.head);
+    my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
+    my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
+    my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+    if constexpr (F::HELP) __syncthreads();   // A: the helper wave's reset states
+    if (done) {
+        if (a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
+            float4 t[kRowF4];
+#pragma unroll
+            for (int k = 0; k < kRowF4; ++k) t[k] = my[k];
+            float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(L.e) * L.D);
+#pragma unroll
+            for (int k = 0; k < kRowF4; ++k) trow[k] = t[k];
+        }
+        if constexpr (F::HELP) {
+            const int t = threadIdx.x;
+            take_reset_state(l.rs_body, t, L.b, L.sc, L.ep);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) o12[k] = l.rs_obs[k * kStepBlock + t];
+        } else {
+            hover_reset_state(a, C, L.e, L.b, L.sc, L.ep);
+            hover_obs12(C, L.b, o12);      // the reset keeps the ring: only the kinematic part changes
+        }
+        my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
+        my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
+        my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
+    }
+    RACE_SET(t4);
+    // the state leaves first: its registers are free before the copy-out (holding both
+    // spilled the copy-out buffer to scratch)
+    chain_store_state(a, L);
+    __syncthreads();   // B (without a helper: the block's rows)
+    float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
+#pragma unroll
+    for (int k = 0; k < F::kChainCols; ++k) store_out(dst + threadIdx.x + kStepBlock * k, l.rows[threadIdx.x + kStepBlock * k]);
+}
+// The chain's end in the row-store kernels: 16-byte stores per lane straight from registers
+template <class F>
+__device__ __forceinline__ void chain_end_rows(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                               ChainLane<F>& L, float o12[12], bool done, [[maybe_unused]] uint64_t& t4) {
+    constexpr int A = F::A, B = F::B;
+    const int E = a.E, e = L.e, D = L.D;
+#pragma unroll
+    for (int p = 0; p < B; ++p) {
+        const bool hit = p == L.head;
+#pragma unroll
+        for (int j = 0; j < A; ++j) L.ring[p][j] = hit ? L.act[j] : L.ring[p][j];
+    }
+    if (done) {
+        if (a.tobs) {
+            if constexpr (B > 0) write_row<A, B>(a.tobs + size_t(e) * D, o12, L.ring, L.head1);
+            else write_row_generic<A>(a.tobs + size_t(e) * D, o12, a.ring, a.B, E, e, L.head1, L.act, true);
+        }
+        hover_reset_state(a, C, e, L.b, L.sc, L.ep);
+        if (L.split) hover_obs12_split(C, L.b, o12);
+        else hover_obs12(C, L.b, o12);
+    }
+    RACE_SET(t4);
+    if constexpr (B > 0) write_row<A, B>(a.obs + size_t(e) * D, o12, L.ring, L.head1);
+    else write_row_generic<A>(a.obs + size_t(e) * D, o12, a.ring, a.B, E, e, L.head1, L.act, true);
+}
+
+template <class F>
+__device__ __forceinline__ void hover_chain_wave(const HoverArgs<typename F::Real>& a, const HoverConst<typename F::Real>& C,
+                                                 typename F::Lds& l, const float* pre) {
+    using Real = typename F::Real;
+    constexpr int A = F::A, B = F::B, SC = F::SC;
+    constexpr bool STG = F::STG, HELP = F::HELP, ANG = F::ANG, TW = F::TW, DRAG = F::DRAG, DYN = F::DYN, LATE_XY = F::LATE_XY;
+    const int E = a.E;
+    ChainLane<F> L;
+    // SPLIT (a step of ONE env, BASELINE config 1: launched or persistent): every lane of the wave runs
+    // env 0 (the same inputs, the same code: the duplicate stores write the same values) so that three
+    // lanes can take the three obs angles at once; contacts are counted by lane 0 alone
+    L.split = !STG && !HELP && E == 1;
+    L.e = L.split ? 0 : int(blockIdx.x) * kStepBlock + int(threadIdx.x);
+    L.D = B > 0 ? 12 + B * A : a.D;
+    if (L.e >= E) return;
+    const int e = L.e;
+    RACE_MARK(t0);
+    L.fit = F::FO == 2 ? field_offsets_fit<Real>(E) : F::FO == 1;
+    L.lag = C.link_lag && !DYN;
+    chain_loads<F>(a, pre, L);
+    Real rpm[4];
+    chain_rpm<F>(a, C, L, rpm);
+    Body<Real>& b = L.b;
     // ---- sub-step loop (BaseAviary.py:347-376) ----
     bool touched = false;
     V3<Real> wbf = v3(Real(0), Real(0), Real(0));   // ANG: the chain's final ω, still in the body frame
-    // ANG with unrolled sub-steps: pos.x / pos.y are summed behind barrier A too (pyb_chain's vxy)
-    constexpr bool LATE_XY = ANG && !DYN && SC > 0 && !TW;
     Real vxy[LATE_XY ? 2 * SC : 2] = {};
 #ifdef ADRP_RACE_TIMING
     // loads landed: the rpm gains and the state are consumed by the first sub-step
@@ -1575,104 +831,39 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         } else {
             for (int s = 0; s < C.S; ++s) dyn_substep(C, b, rpm);
         }
-    } else if constexpr (TW) {   // the rotational half; the z axes of the poses go to the translation wave
-        pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{}, &wbf, nullptr, slot_write);
+    } else if constexpr (TW) {   // the rotational half; the poses go to the translation wave
+        pyb_chain<Real, F::PH, SC, DRAG>(C, b, rpm, L.lag, NoExtForce{}, &wbf, nullptr, l.slots());
     } else {
-        touched = pyb_chain<Real, PH, SC, DRAG>(C, b, rpm, lag, NoExtForce{}, ANG ? &wbf : nullptr, LATE_XY ? vxy : nullptr);
+        touched = pyb_chain<Real, F::PH, SC, DRAG>(C, b, rpm, L.lag, NoExtForce{}, ANG ? &wbf : nullptr, LATE_XY ? vxy : nullptr);
     }
     RACE_MARK(t2);
-    if (touched && a.contact_count && (!split || threadIdx.x == 0)) atomicAdd(a.contact_count, 1);
+    if (touched && a.contact_count && (!L.split || threadIdx.x == 0)) atomicAdd(a.contact_count, 1);
     // ---- action ring: append this action at `head` (deque.append, BaseRLAviary.py:187) ----
     if constexpr (HELP) {
         // the helper wave appends
     } else if constexpr (A == 4)
-        reinterpret_cast<float4*>(a.ring)[size_t(head) * E + e] = make_float4(act[0], act[1], act[2], act[3]);
+        reinterpret_cast<float4*>(a.ring)[size_t(L.head) * E + e] = make_float4(L.act[0], L.act[1], L.act[2], L.act[3]);
     else
 #pragma unroll
-        for (int j = 0; j < A; ++j) a.ring[(size_t(head) * E + e) * A + j] = act[j];
+        for (int j = 0; j < A; ++j) a.ring[(size_t(L.head) * E + e) * A + j] = L.act[j];
     const int BB = B > 0 ? B : a.B;                    // ring length (runtime for the generic kernel)
-    const int head1 = head + 1 == BB ? 0 : head + 1;
-    // the state and the ints leave through the offsets of the loads
-    auto store_state = [&]() {
-        if (fit) {
-            store_body_at<Real>(a.f, fo, b, lag, DRAG, DYN);
-            field_last(a.ist, io[HI_STEP]) = sc;
-            field_last(a.ist, io[HI_EPISODE]) = ep;
-            field_last(a.ist, io[HI_RING_HEAD]) = head1;
-            field_form_end();
-        } else {
-            store_body(a, e, b, lag, DRAG, DYN);
-            a.ist[HI_STEP * E + e] = sc;
-            a.ist[HI_EPISODE * E + e] = ep;
-            a.ist[HI_RING_HEAD * E + e] = head1;
-        }
-    };
+    L.head1 = L.head + 1 == BB ? 0 : L.head + 1;
     // ---- obs / reward / terminated / truncated (HoverAviary.py:68-117) ----
     float o12[12];
     V3<Real> rpy;
-    if constexpr (ANG) {
-        const int tl = threadIdx.x;
-        ang_q[tl] = b.q.x; ang_q[kStepBlock + tl] = b.q.y; ang_q[2 * kStepBlock + tl] = b.q.z;
-        ang_q[3 * kStepBlock + tl] = b.q.w;
-#ifdef ADRP_RACE_TIMING
-        [[maybe_unused]] const uint64_t t_a = __builtin_amdgcn_s_memtime();   // the chain's arrival at A
-#endif
-        __syncthreads();   // A: the quaternion out; the reset helper's states and ring rows in
-#ifdef ADRP_RACE_TIMING
-        if constexpr (TW) {   // [20] / [21]: cycles the translation wave arrived at A before / behind the chain
-            if (threadIdx.x == 0) {
-                const uint64_t t_w = tw_time[0];
-                atomicAdd(&g_race_phase[t_a >= t_w ? 20 : 21], (unsigned long long)(t_a >= t_w ? t_a - t_w : t_w - t_a));
-            }
-        }
-#endif
-        if constexpr (TW) {   // the translation wave's final pos / vel, read while the chain has arithmetic to do
-            const Real* src = tw_out + threadIdx.x;
-            b.pos = v3(src[(HF_POS + 0) * kStepBlock], src[(HF_POS + 1) * kStepBlock], src[(HF_POS + 2) * kStepBlock]);
-            b.vel = v3(src[(HF_VEL + 0) * kStepBlock], src[(HF_VEL + 1) * kStepBlock], src[(HF_VEL + 2) * kStepBlock]);
-        }
-        // while the three helper waves take one angle each, the chain does what only it can: ω back to the
-        // world frame (deferred by pyb_chain), the conversions, the reward and the angle-free truncation tests
-        // (hold: arithmetic carries no order against a barrier, and the compiler had placed most of this
-        // before A and the rest after C, leaving the chain to wait at C with nothing to do; what the work
-        // starts from is taken behind A here, and what it gives is finished before C below)
-        hold(b.q.x); hold(b.q.y); hold(b.q.z); hold(b.q.w);
-        hold(wbf.x); hold(wbf.y); hold(wbf.z);
-        if constexpr (!TW) { hold(b.pos.x); hold(b.pos.y); hold(b.pos.z); }
-        if constexpr (LATE_XY) {   // the horizontal position sums of the sub-steps, deferred to here
-#pragma unroll
-            for (int k = 0; k < 2 * SC; ++k) hold(vxy[k]);
-#pragma unroll
-            for (int s = 0; s < SC; ++s) {
-                b.pos.x = fmx(C.dt, vxy[2 * s], b.pos.x);
-                b.pos.y = fmx(C.dt, vxy[2 * s + 1], b.pos.y);
-            }
-        }
-        if constexpr (!TW) { hold(b.vel.x); hold(b.vel.y); hold(b.vel.z); }
-        if constexpr (!DYN) b.w = mul(rot_fm(b.q), wbf);
-        const V3<Real> w = C.physics == ADRP_PHYS_DYN ? b.angv : b.w;   // hover_obs12's row, the angles below
-        if constexpr (!TW) {   // (TW: row floats 0-2 and 6-8 are the translation wave's)
-            o12[0] = float(b.pos.x); o12[1] = float(b.pos.y); o12[2] = float(b.pos.z);
-            o12[6] = float(b.vel.x); o12[7] = float(b.vel.y); o12[8] = float(b.vel.z);
-        }
-        o12[9] = float(w.x);     o12[10] = float(w.y);    o12[11] = float(w.z);
-    } else if (split) {
-        rpy = hover_obs12_split(C, b, o12);
-    } else {
-        rpy = hover_obs12(C, b, o12);
-    }
+    if constexpr (ANG) chain_row_behind_A<F>(C, l, b, wbf, vxy, o12);
+    else if (L.split) rpy = hover_obs12_split(C, b, o12);
+    else rpy = hover_obs12(C, b, o12);
     bool te, tr;
-    if constexpr (TW) {   // the translation wave's flag byte: terminated, a position limit passed
-        const uint8_t fl = tw_flag[threadIdx.x];
+    if constexpr (TW) {   // the translation wave's flag byte
+        const uint8_t fl = l.tw_flag[threadIdx.x];
         te = (fl & 1) != 0;
-        tr = (fl & 2) != 0 || sc >= C.trunc_steps;
+        tr = (fl & 2) != 0 || L.sc >= C.trunc_steps;
     } else {
-        const Real dx = C.target[0] - b.pos.x, dy = C.target[1] - b.pos.y, dz = C.target[2] - b.pos.z;
-        const Real d2 = dx * dx + dy * dy + dz * dz;
-        const Real r = Real(2) - d2 * d2;
-        a.rew[e] = float(r > Real(0) ? r : Real(0));
-        te = d2 < Real(1e-8);   // |target - pos| < 1e-4
-        tr = fabs_(b.pos.x) > Real(1.5) || fabs_(b.pos.y) > Real(1.5) || b.pos.z > Real(2.0) || sc >= C.trunc_steps;
+        const PosFlags pf = hover_pos_flags(C, b.pos);
+        a.rew[e] = pf.rew;
+        te = pf.term;
+        tr = pf.out || L.sc >= C.trunc_steps;
     }
     [[maybe_unused]] bool slow = false;   // ANG: the chain has waited at C for the angles
     if constexpr (ANG) {
@@ -1691,8 +882,8 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         slow = __any(!sure);
         if (__builtin_expect(slow, 0)) {
             __syncthreads();   // C: the helpers' roll and pitch
-            rpy.x = ang_r[threadIdx.x];
-            rpy.y = ang_p[threadIdx.x];
+            rpy.x = l.ang_r[threadIdx.x];
+            rpy.y = l.ang_p[threadIdx.x];
             over = fabs_(rpy.x) > Real(0.4) || fabs_(rpy.y) > Real(0.4);
         }
         tr = tr || over;
@@ -1701,150 +892,18 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
     }
     if constexpr (!TW) a.term[e] = te;
     a.trunc[e] = tr;
-    sc += C.S;
+    L.sc += C.S;
     const bool done = a.autoreset && (te || tr);
     RACE_MARK(t3);
 #ifdef ADRP_RACE_TIMING
     const unsigned long long dmask = __ballot(done);
-    uint64_t t4 = 0;
 #endif
-    if constexpr (STG) {
-        // The obs row is assembled in LDS (18 float4 per lane, no padding: the copy-out
-        // reads contiguous float4s at immediate offsets) and leaves as one coalesced block.
-        static_assert(A == 4 && B == 15, "staged rows: 72-float rows only");
-        float4* my = rows + threadIdx.x * kRowF4;
-        // Every env appends once per env.step and resets keep the ring, so the ring head is
-        // the same for every env in practice: then the slot -> row position map is scalar
-        // and the appended action simply overwrites the newest position.
-        const int hu = __builtin_amdgcn_readfirstlane(head);
-        if constexpr (HELP) {
-            // the ring part of the row is staged by the helper wave
-        } else if (__all(head == hu)) {
-            const int h1 = hu + 1 == B ? 0 : hu + 1;
-#pragma unroll
-            for (int p = 0; p < B; ++p) {
-                const int k = p >= h1 ? p - h1 : p - h1 + B;
-                my[3 + k] = make_float4(ring[p][0], ring[p][1], ring[p][2], ring[p][3]);
-            }
-            my[3 + B - 1] = make_float4(act[0], act[1], act[2], act[3]);
-        } else {
-#pragma unroll
-            for (int p = 0; p < B; ++p) {
-                const bool hit = p == head;
-#pragma unroll
-                for (int j = 0; j < A; ++j) ring[p][j] = hit ? act[j] : ring[p][j];
-            }
-            stage_row<A, B>(my, o12, ring, head1);
-        }
-        if constexpr (TROWS) {
-            // the chain's end: its nine floats of the row (the helper waves write floats 3, 4, 5), the done marks
-            // for the helper waves' tail, the reset state of its done lanes, the state stores
-            float* mf = reinterpret_cast<float*>(my);
-            if constexpr (TW) {
-                mf[9] = o12[9]; mf[10] = o12[10]; mf[11] = o12[11];
-            } else {
-                mf[0] = o12[0]; mf[1] = o12[1]; mf[2] = o12[2];
-                mf[6] = o12[6]; mf[7] = o12[7];
-                my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-            }
-            const unsigned long long done_mask = __ballot(done);
-            done_b[threadIdx.x] = done;
-            done_cnt[0] = a.tobs ? __popcll(done_mask) : 0;   // (every lane writes the same word)
-            if (done) {
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(uint32_t(done_mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(done_mask), 0u));
-                done_list[rank] = uint8_t(threadIdx.x);
-                const int t = threadIdx.x;   // BaseAviary.reset from the helper's LDS copy
-                Real v[kResetFields];
-#pragma unroll
-                for (int k = 0; k < kResetFields; ++k) v[k] = rs_body[k * kStepBlock + t];
-                b.pos = v3(v[0], v[1], v[2]);
-                b.q = {v[3], v[4], v[5], v[6]};
-                b.ql = b.q;
-                b.vel = v3(v[7], v[8], v[9]);
-                b.w = v3(v[10], v[11], v[12]);
-                b.angv = v3(v[13], v[14], v[15]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
-                sc = 0;
-                ep += 1;
-            }
-            RACE_SET(t4);
-            store_state();
-            if (!slow) __syncthreads();   // C (the unsure wave passed it above)
-            __syncthreads();              // B: the helper waves copy out
-        } else {
-            my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-            my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-            my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-            if constexpr (HELP) __syncthreads();   // A: the helper wave's reset states
-            if (done) {
-                if (a.tobs) {   // terminal obs = the row just staged (this lane's own LDS row)
-                    float4 t[kRowF4];
-#pragma unroll
-                    for (int k = 0; k < kRowF4; ++k) t[k] = my[k];
-                    float4* trow = reinterpret_cast<float4*>(a.tobs + size_t(e) * D);
-#pragma unroll
-                    for (int k = 0; k < kRowF4; ++k) trow[k] = t[k];
-                }
-                if constexpr (HELP) {   // BaseAviary.reset from the helper's LDS copy
-                    const int t = threadIdx.x;
-                    Real v[kResetFields];
-#pragma unroll
-                    for (int k = 0; k < kResetFields; ++k) v[k] = rs_body[k * kStepBlock + t];
-                    b.pos = v3(v[0], v[1], v[2]);
-                    b.q = {v[3], v[4], v[5], v[6]};
-                    b.ql = b.q;
-                    b.vel = v3(v[7], v[8], v[9]);
-                    b.w = v3(v[10], v[11], v[12]);
-                    b.angv = v3(v[13], v[14], v[15]);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) b.prev_rpm[i] = Real(0);
-                    sc = 0;
-                    ep += 1;
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) o12[k] = rs_obs[k * kStepBlock + t];
-                } else {
-                    hover_reset_state(a, C, e, b, sc, ep);
-                    hover_obs12(C, b, o12);      // the reset keeps the ring: only the kinematic part changes
-                }
-                my[0] = make_float4(o12[0], o12[1], o12[2], o12[3]);
-                my[1] = make_float4(o12[4], o12[5], o12[6], o12[7]);
-                my[2] = make_float4(o12[8], o12[9], o12[10], o12[11]);
-            }
-            RACE_SET(t4);
-            // the state leaves first: its registers are free before the copy-out (holding both
-            // spilled the copy-out buffer to scratch)
-            store_state();
-            __syncthreads();
-            float4* dst = reinterpret_cast<float4*>(a.obs) + size_t(blockIdx.x) * kStepBlock * kRowF4;
-            constexpr int KC = cb(1);   // HELP: the helper wave copies the other columns
-#pragma unroll
-            for (int k = 0; k < KC; ++k) store_out(dst + threadIdx.x + kStepBlock * k, rows[threadIdx.x + kStepBlock * k]);
-        }
-    } else {
-#pragma unroll
-        for (int p = 0; p < B; ++p) {
-            const bool hit = p == head;
-#pragma unroll
-            for (int j = 0; j < A; ++j) ring[p][j] = hit ? act[j] : ring[p][j];
-        }
-        if (done) {
-            if (a.tobs) {
-                if constexpr (B > 0) write_row<A, B>(a.tobs + size_t(e) * D, o12, ring, head1);
-                else write_row_generic<A>(a.tobs + size_t(e) * D, o12, a.ring, a.B, E, e, head1, act, true);
-            }
-            hover_reset_state(a, C, e, b, sc, ep);
-            if (split) hover_obs12_split(C, b, o12);
-            else hover_obs12(C, b, o12);
-        }
-        RACE_SET(t4);
-        if constexpr (B > 0) write_row<A, B>(a.obs + size_t(e) * D, o12, ring, head1);
-        else write_row_generic<A>(a.obs + size_t(e) * D, o12, a.ring, a.B, E, e, head1, act, true);
-    }
+    [[maybe_unused]] uint64_t t4 = 0;
+    if constexpr (ANG) chain_end_helpers<F>(a, l, L, o12, done, slow, t4);
+    else if constexpr (STG) chain_end_staged<F>(a, C, l, L, o12, done, t4);
+    else chain_end_rows<F>(a, C, L, o12, done, t4);
     RACE_MARK(t5);
-    if constexpr (!STG) {
-        store_state();
-    }
+    if constexpr (!STG) chain_store_state(a, L);
 #ifdef ADRP_RACE_TIMING
     RACE_MARK(t6);
     if (threadIdx.x == 0) {   // [loads, sub-steps, obs+flags, reset, obs row, state stores, total, -, waves]
@@ -1854,6 +913,50 @@ __device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const 
         if (dmask) atomicAdd(&g_race_phase[9], 1ull);
     }
 #endif
+}
+
+// The step: the workgroup's LDS and one role per wave.  Who passes which barrier, once each, behind what:
+//            chain wave (0)                      reset helper (1, HELP)          angle helpers (2 and 3, ANG)
+//   head     pyb_chain's pre-loop, ahead of      its entry                       wave 3's loads and mark clears
+//   (TW)     the first pose (hand.head())
+//   A        its final quaternion in LDS;        reset states, ring rows and     wave 3: the translation's
+//   (HELP)   fp32: its kinematic row floats      the ring append                 pos / vel / flags in LDS
+//   C        sure tilt: its state stores;        the roll, its ring columns      pitch (2), yaw (3), their
+//   (ANG)    unsure: ahead of reading roll                                       ring columns
+//            and pitch, then the state stores
+//   B        C, or fp32 its state stores         C, or fp32 A                    C
+//   then     fp32: columns 0-8 out; ANG: ends    fp32: columns 9-17 out; ANG:    helper_tail
+//                                                helper_tail
+template <typename Real, int PH, int A, int B, int SC, bool STG = false, int CTL = 0, bool HELP = false, int SYS = 0,
+          int FO = 2>
+__device__ __forceinline__ void hover_step_body(const HoverArgs<Real>& a, const HoverConst<Real>& C,
+                                                const float* pre = nullptr) {
+    using F = StepForm<Real, PH, A, B, SC, STG, CTL, HELP, SYS, FO>;
+    using Lds = typename F::Lds;
+    constexpr bool ANG = F::ANG, TW = F::TW;
+    constexpr int kLane = kStepBlock;   // (an array the kernel does not have is one element that nothing names)
+    __shared__ float4 rows[Lds::kRows];
+    __shared__ typename Lds::Slots::Real2 tw_q[TW ? 2 * SC * kLane : 1];
+    __shared__ Real rs_body[HELP ? kResetFields * kLane : 1], tw_out[TW ? Lds::kTwOut * kLane : 1];
+    __shared__ Real ang_q_own[ANG && !TW ? 4 * kLane : 1], ang_r[ANG ? kLane : 1], ang_p[ANG ? kLane : 1];
+    __shared__ float rs_obs[HELP && !ANG ? 12 * kLane : 1], ang_y[ANG ? kLane : 1];
+    __shared__ int done_cnt[1], tw_mark[TW ? Lds::Slots::kSlots : 1];
+    __shared__ uint8_t done_list[ANG ? kLane : 1], done_b[ANG ? kLane : 1], tw_flag[TW ? kLane : 1];
+#ifdef ADRP_RACE_TIMING
+    __shared__ unsigned long long tw_time[1];
+    Lds lds = {rows, tw_q, rs_body, tw_out, ang_q_own, ang_r, ang_p, rs_obs, ang_y, done_cnt, tw_mark, done_list, done_b,
+               tw_flag, tw_time};
+#else
+    Lds lds = {rows, tw_q, rs_body, tw_out, ang_q_own, ang_r, ang_p, rs_obs, ang_y, done_cnt, tw_mark, done_list, done_b,
+               tw_flag};
+#endif
+    if constexpr (F::ANG) {
+        if (threadIdx.x >= 2 * kStepBlock) return hover_angle_helper<F>(a, C, lds);
+    }
+    if constexpr (HELP) {
+        if (threadIdx.x >= kStepBlock) return hover_reset_helper<F>(a, C, lds);
+    }
+    hover_chain_wave<F>(a, C, lds, pre);
 }
 
 // Arguments the step needs at wave start are separate scalars so the CP preloads them into

@@ -13,7 +13,7 @@
 namespace adrp {
 
 template <typename Real>
-struct Body;    // hover_kernel.h
+struct Body;    // hover_dynamics.h
 template <typename Real>
 struct Chain;
 

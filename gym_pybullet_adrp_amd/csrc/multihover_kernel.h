@@ -12,12 +12,12 @@
 // its functions (shared with ctrl_kernel.h).  A live lane only ever reads lanes of its own group, so an
 // env's results do not depend on E or on where the env sits in the batch.
 //
-// The sub-step body is hover_kernel.h's (pyb_chain / pyb_substep / dyn_substep); the downwash enters it
+// The sub-step body is hover_dynamics.h's (pyb_chain / pyb_substep / dyn_substep); the downwash enters it
 // as one more world-frame force (pyb_substep's Fext).  State, ints and ring use HoverAviary's layout
 // with E N columns, column e N + n; the per-env ints are replicated on the env's columns.
 #pragma once
 
-#include "hover_kernel.h"
+#include "hover_dynamics.h"
 #include "lane_group.h"
 
 namespace adrp {

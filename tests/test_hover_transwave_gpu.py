@@ -24,7 +24,7 @@ from test_hover_tail_gpu import (BENCH_NOISE, PATTERNS, REFERENCE, SENTINEL, ass
 from test_hover_chainend_gpu import INSIDE, LIMIT  # noqa: E402
 
 KERNEL = {"fp64": "hover_step<f64,PYB,A4,B15,cf2x>", "fp32": "hover_step<f32,PYB,A4,B15,cf2x>"}
-COLL_HH, COLL_R = 0.0125, 0.06   # cf2x collision cylinder: half height, radius (csrc/hover_kernel.h, cf2x_consts)
+COLL_HH, COLL_R = 0.0125, 0.06   # cf2x collision cylinder: half height, radius (csrc/hover_dynamics.h, cf2x_consts)
 
 
 def start_states(E, seed, tilt=0.2):
