@@ -168,6 +168,10 @@ def load():
         lib.adrp_race_roster_done.restype = I
     lib.adrp_race_plan.argtypes = [P, P]
     lib.adrp_race_plan.restype = I
+    lib.adrp_race_camera.argtypes = [P, P]
+    lib.adrp_race_camera.restype = I
+    lib.adrp_race_camera_env.argtypes = [P, P, P]
+    lib.adrp_race_camera_env.restype = I
     lib.adrp_dslpid_default_params.argtypes = [I, P]
     lib.adrp_dslpid_default_params.restype = I
     lib.adrp_dslpid_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]

@@ -11,6 +11,13 @@ The reference returns reward 0; ``reward="wrapper"`` computes utils/wrapper.py's
 RewardWrapper instead.  The Mellinger controllers that the reference runs in one OS
 process per drone are fused into the kernel (500 Hz).
 
+``obs=ObservationType.RGB`` returns the drones' camera images instead of the rows: uint8
+[E, N, 48, 64, 4] (space Box(0, 255, (N, 48, 64, 4), uint8), MultiRaceAviary.py:300-304), rendered by one
+camera launch after the step launch on the same stream (camera.py; DESIGN.md §3.19 states the deviations
+from pybullet's renderer; the reference casts the images to float32).  The rows stay at ``env.kin_obs``,
+depth and segmentation at ``env.camera.dep`` / ``env.camera.seg``; ``info["terminal_observation"]`` stays
+the rows.
+
 Batched extras: ``num_envs``, ``device``, ``precision``, ``seed``, ``autoreset``,
 ``env_offset``, ``link_frame_lag``.  step/reset return persistent device tensors.
 
@@ -58,8 +65,8 @@ class MultiRaceAviary(AviaryEnv):
             raise ValueError(f"DroneModel {drone_model} not supported (cf2x_IROS.urdf constants only)")
         if gui or record:
             raise ValueError("GUI / video recording are out of scope (DESIGN.md)")
-        if obs != ObservationType.KIN:
-            raise ValueError("only ObservationType.KIN is supported")
+        if obs not in (ObservationType.KIN, ObservationType.RGB):
+            raise ValueError("only ObservationType.KIN and ObservationType.RGB are supported")
         if pyb_freq % ctrl_freq != 0:
             raise ValueError("[ERROR] in BaseAviary.__init__(), pyb_freq is not divisible by env_freq.")
         if reward not in ("env", "wrapper"):
@@ -92,6 +99,7 @@ class MultiRaceAviary(AviaryEnv):
                                     list(cfg.track.bounds_hi)])
         self.action_scale = np.array([1, 1, 1, np.pi])
         self.num_envs = cfg.num_envs
+        self.IMG_RES = np.array([64, 48])          # BaseAviary.py:135
         self.action_space = self._actionSpace()
         self.observation_space = self._observationSpace()
         E, N, D = self.num_envs, self.NUM_DRONES, self.h.D
@@ -103,6 +111,11 @@ class MultiRaceAviary(AviaryEnv):
         self._act_shape = (E, N, 4)
         self._info = {"answer": 42, "terminal_observation": self._tobs}
         self._last_act = None      # the last ndarray (FULLSTATE) action tensor, by reference
+        # obs=RGB: the drones' camera (camera.py), one launch after every step / reset launch on the same stream
+        self.camera = None
+        if obs == ObservationType.RGB:
+            from ..camera import DroneCamera
+            self.camera = DroneCamera(self, int(self.IMG_RES[0]), int(self.IMG_RES[1]), capture="reference")
         self.commands = False
         if commands:
             self.enable_commands()
@@ -113,6 +126,9 @@ class MultiRaceAviary(AviaryEnv):
         return Box(low=-1 * lim, high=lim, dtype=float)
 
     def _observationSpace(self):
+        if self.observation_type == ObservationType.RGB:      # MultiRaceAviary.py:300-304
+            return Box(low=0, high=255, shape=(self.NUM_DRONES, int(self.IMG_RES[1]), int(self.IMG_RES[0]), 4),
+                       dtype=np.uint8)
         lo = np.concatenate([[-5] * 3, [-np.pi] * 3, [-10] * 3, [-10] * 3, [-5, -5, -5, -np.pi] * 4, [-1] * 4,
                              [-5] * 12, [-1] * 4, [-1]])
         hi = np.concatenate([[5] * 3, [np.pi] * 3, [10] * 3, [10] * 3, [5, 5, 5, np.pi] * 4, [1] * 4,
@@ -125,7 +141,7 @@ class MultiRaceAviary(AviaryEnv):
     # ---- gymnasium-style API, batched ----
     def reset(self, seed: int = None, options: dict = None, mask=None):
         """Reset all envs (or those with mask[e] != 0); `seed` re-keys the random streams first.
-        Returns (obs [E,N,D], info)."""
+        Returns (obs [E,N,D], info); with obs=RGB the images uint8 [E,N,48,64,4]."""
         m = None
         if mask is not None:
             m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
@@ -138,7 +154,20 @@ class MultiRaceAviary(AviaryEnv):
         self.h.reset(self._obs, m)
         if m is None:
             self._last_act = None
-        return self._obs, {"answer": 42}
+        return self._observe(m), {"answer": 42}
+
+    @property
+    def kin_obs(self):
+        """the kinematic rows [E,N,D] of the last step / reset, whatever the observation type"""
+        return self._obs
+
+    def _observe(self, mask=None):
+        """what step / reset return as the observation: the KIN rows, or with obs=RGB the colour images
+        rendered now from the state the launch before left (MultiRaceAviary.py:574-588: drones whose
+        step_counter is a multiple of IMG_CAPTURE_FREQ; envs the step reset show their reset state)"""
+        if self.camera is None:
+            return self._obs
+        return self.camera.render(mask)["rgb"]
 
     def enable_commands(self):
         """High-level command mode (include/adrp.h adrp_enable_commands): step() then also takes
@@ -192,11 +221,11 @@ class MultiRaceAviary(AviaryEnv):
             self.enable_commands()
             self.h.command(*action)
             self.h.step(None, self._obs, self._rew, self._term, self._trunc, self._tobs)
-            return self._obs, self._rew, self._term, self._trunc, self._info
+            return self._observe(), self._rew, self._term, self._trunc, self._info
         if isinstance(action, (list, tuple)) and not _numeric(action):
             self.command(action)
             self.h.step(None, self._obs, self._rew, self._term, self._trunc, self._tobs)
-            return self._obs, self._rew, self._term, self._trunc, self._info
+            return self._observe(), self._rew, self._term, self._trunc, self._info
         act = action
         if not (isinstance(act, torch.Tensor) and act.dtype == torch.float32 and act.device == self.device
                 and act.is_contiguous() and act.shape == self._act_shape):
@@ -204,7 +233,7 @@ class MultiRaceAviary(AviaryEnv):
             act = act.contiguous()
         self.h.step(act, self._obs, self._rew, self._term, self._trunc, self._tobs)
         self._last_act = act
-        return self._obs, self._rew, self._term, self._trunc, self._info
+        return self._observe(), self._rew, self._term, self._trunc, self._info
 
     def set_noise(self, act_noise=None, force=None):
         """Parity mode: the next steps take the action noise [E, N, S, 4] and the disturbance force

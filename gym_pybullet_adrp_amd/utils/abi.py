@@ -221,3 +221,13 @@ class AdrpRacePlanIO(ctypes.Structure):
                 ("obs_stride", _i32), ("reserved", _i32),
                 ("obs", _p), ("mask", _p), ("samples", _p), ("ref", _p), ("status", _p),
                 ("knots", _p), ("n_knots", _p), ("coef", _p), ("phase", _p)]
+
+
+class AdrpRaceCameraIO(ctypes.Structure):
+    """adrp_race_camera_io (include/adrp.h): the scene, the state planes and the caller-owned images of the drone camera"""
+    _p = ctypes.c_void_p
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_envs", _i32), ("num_drones", _i32), ("width", _i32),
+                ("height", _i32), ("num_gates", _i32), ("num_obstacles", _i32), ("gate_low", _arr(_i32, 4)),
+                ("precision", _i32), ("capture_freq", _i32), ("reserved", _i32),
+                ("pos", _p), ("quat", _p), ("gates", _p), ("obstacles", _p), ("step_counter", _p), ("mask", _p),
+                ("dep", _p), ("seg", _p), ("rgb", _p)]

@@ -783,6 +783,67 @@ typedef struct adrp_race_plan_io {
 int adrp_race_plan(const adrp_race_plan_io* io, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Drone camera of the race scene (BaseAviary._getDroneImages, BaseAviary.py:569-621; the RGB observation of
+ * MultiRaceAviary, MultiRaceAviary.py:300-304, 574-588): depth, segmentation and colour images of every
+ * (env, drone) in one launch, by ray casting against the scene's analytic shapes: the ground plane, the
+ * gates' and obstacles' URDF boxes and cylinders at the env's poses, the env's other drones as their
+ * collision cylinders.  csrc/camera_core.h (view, part table, ray tests; shared with the CPU program
+ * csrc/camera_host.cpp), csrc/camera_kernel.h.  Handle-less like the planner above: the caller owns every
+ * buffer, all on one device.  DESIGN.md §3.19 states the camera model and its deviations from pybullet.
+ *
+ * View of drone slot e * N + n: eye = pos + (0, 0, L), L = 0.0397; forward f along R(quat) (1000, 0, 0) + pos -
+ * eye, up = world z; 60 degrees vertical field of view, aspect 1, near = L, far = 1000.  Pixel (row i from the
+ * top, column j) casts d = f + x s + y u, x = (2 (j + .5) / W - 1) tan 30, y = (1 - 2 (i + .5) / H) tan 30; the
+ * nearest entry with near <= t <= far wins (t is the eye-space depth).
+ * Outputs, each optional, contiguous [E][N][H][W]:
+ *   dep float32: far / (far - near) (1 - near / t); 1 where nothing is hit
+ *   seg int32:   body id + ((link + 1) << 24); plane 0, drone n -> 1 + n, gate g -> 1 + N + g, obstacle o ->
+ *                1 + N + G + o; gate links: bottom bar 0, top 1, +x 2, -x 3, support 4; obstacle: cylinder -1,
+ *                box 0; plane and drones -1; -1 where nothing is hit
+ *   rgb uint8 [E][N][H][W][4]: the hit link's URDF material colour, alpha 255, unlit; 0 0 0 0 where nothing is hit
+ * State planes as adrp_get_state lays them out, column e * N + n of E * N, float (precision 0) or double (1):
+ * pos [3] (pos_x..z), quat [4] (quat_x..w), gates [16] (gate_g_x, _y, _z, _yaw), obstacles [12] (obst_o_x, _y, _z).
+ * capture_freq > 0: only the (env, drone) with step_counter[e * N + n] % capture_freq == 0 are rendered
+ * (BaseAviary.step's IMG_CAPTURE_FREQ test), the other images stay as they are; 0 renders all.  With a
+ * mask only the envs with mask[e] != 0 are rendered.
+ *
+ * adrp_race_camera_env reads the state planes, the step counters and the track (num_gates, num_obstacles,
+ * gate types) of a race handle instead of the io's (its state pointers and scene fields are ignored).
+ *
+ * Refused with ADRP_ERR_INVALID before any device call, through adrp_last_error(NULL): a NULL io, a
+ * struct_size mismatch, num_envs < 1, num_drones outside 1..ADRP_MAX_DRONES, width or height < 1,
+ * num_envs * num_drones at 2^24 or more (one workgroup each), num_envs * num_drones * height * width past
+ * 2^31 - 1, no output pointer, an output pointer not 4-byte aligned, a negative capture_freq;
+ * handle-less: num_gates / num_obstacles outside 0..4, precision not 0 / 1, a NULL pos / quat (gates /
+ * obstacles when their count is not 0), capture_freq > 0 without step_counter; _env: a NULL handle, a handle
+ * in persistent mode, a non-race handle, a handle of another E or N.
+ * --------------------------------------------------------------------------------------- */
+typedef struct adrp_race_camera_io {
+    uint32_t struct_size;     /* sizeof(adrp_race_camera_io); checked */
+    int32_t  num_envs;        /* E >= 1 */
+    int32_t  num_drones;      /* N in 1..ADRP_MAX_DRONES */
+    int32_t  width;           /* W >= 1 */
+    int32_t  height;          /* H >= 1 */
+    int32_t  num_gates;       /* 0..ADRP_MAX_GATES */
+    int32_t  num_obstacles;   /* 0..ADRP_MAX_OBSTACLES */
+    int32_t  gate_low[4];     /* gate g is a low portal (adrp_track.gates[g][6] > 0) */
+    int32_t  precision;       /* of the state planes: 0 float, 1 double */
+    int32_t  capture_freq;    /* 0: always */
+    int32_t  reserved;
+    const void* pos;          /* [3][E*N] */
+    const void* quat;         /* [4][E*N] */
+    const void* gates;        /* [16][E*N] */
+    const void* obstacles;    /* [12][E*N] */
+    const int32_t* step_counter;   /* [E*N], or NULL with capture_freq 0 */
+    const uint8_t* mask;      /* [E] or NULL: every env */
+    float*   dep;             /* [E][N][H][W] out, or NULL */
+    int32_t* seg;             /* [E][N][H][W] out, or NULL */
+    uint8_t* rgb;             /* [E][N][H][W][4] out, 4-byte aligned, or NULL */
+} adrp_race_camera_io;
+int adrp_race_camera(const adrp_race_camera_io* io, void* stream);
+int adrp_race_camera_env(const adrp_race_camera_io* io, adrp_t* h, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Stand-alone batched DSLPIDControl (control/DSLPIDControl.py:9-259, control/BaseControl.py:21-95):
  * what examples/pid.py:126-147 and examples/downwash.py build one object per drone of, for users who
  * drive CtrlAviary themselves.  One controller handle holds `rows` independent controllers (one per
