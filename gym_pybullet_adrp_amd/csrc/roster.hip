@@ -7,14 +7,11 @@
 
 #include <stdint.h>
 
-#include <string>
-
 #include "adrp_internal.h"
+#include "race_host_checks.h"
 #include "roster_kernel.h"
 
 namespace {
-
-int roster_err(const char* fn, const std::string& why) { return seterr(nullptr, ADRP_ERR_INVALID, std::string(fn) + ": " + why); }
 
 // the roster itself (sizes, roles, learner_index): returns nullptr when usable; who: learner l -> its drone
 const char* roster_error(const adrp_race_roster_io* io, RosterLearners* who) {
@@ -61,24 +58,13 @@ const char* buffers_error(const adrp_race_roster_io* io) {
     return nullptr;
 }
 
-// the agents io of the compact step: agents.hip's checks, and the roster's shape
+// the agents io of the compact step: in the roster's shape (asked once its struct_size says the fields are there), and
+// usable by agents.hip's checks
 const char* agents_error(const adrp_race_roster_io* io, const adrp_race_agents_io* ag) {
     if (!ag) return "the agents io is NULL";
-    if (ag->struct_size != sizeof(adrp_race_agents_io)) return "adrp_race_agents_io.struct_size mismatch (ABI)";
-    if (ag->num_envs != io->num_envs || ag->num_drones != io->num_drones)
+    if (ag->struct_size == sizeof(adrp_race_agents_io) && (ag->num_envs != io->num_envs || ag->num_drones != io->num_drones))
         return "the agents io's num_envs, num_drones differ from the roster's";
-    if (ag->obs_dim < ADRP_AGENTS_OBS_MIN) return "obs_dim must be at least 49 (the gate id is column 48)";
-    if (ag->num_gates < 0 || ag->num_gates > ADRP_MAX_GATES) return "num_gates must be in 0..ADRP_MAX_GATES";
-    if ((long long)ag->num_envs * ag->num_drones * ag->obs_dim > 0x7fffffffLL) return "num_envs * num_drones * obs_dim is too large";
-    if (!ag->wr_gate || !ag->wr_target || !ag->wr_prev || !ag->alive || !ag->run_return || !ag->run_length)
-        return "NULL buffer in adrp_race_agents_io";
-    return nullptr;
-}
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(nullptr, ADRP_ERR_DEVICE, std::string(what) + " launch: " + hipGetErrorString(e));
-    return ADRP_OK;
+    return agents_io_error(ag);
 }
 
 int slot_grid(const adrp_race_roster_io* io) { return (io->num_envs * io->num_drones + kRosterLanes - 1) / kRosterLanes; }
@@ -98,8 +84,8 @@ int step_launch(const adrp_race_roster_io* io, const RosterLearners& who, const 
 
 extern "C" int adrp_race_roster_act(const adrp_race_roster_io* io, void* stream) {
     RosterLearners who;
-    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_act", why);
-    if (const char* why = buffers_error(io)) return roster_err("adrp_race_roster_act", why);
+    if (const char* why = roster_error(io, &who)) return refuse("adrp_race_roster_act", why);
+    if (const char* why = buffers_error(io)) return refuse("adrp_race_roster_act", why);
     StreamDeviceGuard g((hipStream_t)stream);
     hipLaunchKernelGGL(race_roster_act_kernel, dim3(slot_grid(io)), dim3(kRosterLanes), 0, (hipStream_t)stream, *io);
     return launched("race roster act");
@@ -107,8 +93,8 @@ extern "C" int adrp_race_roster_act(const adrp_race_roster_io* io, void* stream)
 
 extern "C" int adrp_race_roster_tick(const adrp_race_roster_io* io, const uint8_t* mask, void* stream) {
     RosterLearners who;
-    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_tick", why);
-    if (const char* why = buffers_error(io)) return roster_err("adrp_race_roster_tick", why);
+    if (const char* why = roster_error(io, &who)) return refuse("adrp_race_roster_tick", why);
+    if (const char* why = buffers_error(io)) return refuse("adrp_race_roster_tick", why);
     StreamDeviceGuard g((hipStream_t)stream);
     hipLaunchKernelGGL(race_roster_tick_kernel, dim3(slot_grid(io)), dim3(kRosterLanes), 0, (hipStream_t)stream, *io, mask);
     return launched("race roster tick");
@@ -119,12 +105,10 @@ extern "C" int adrp_race_roster_step(const adrp_race_roster_io* io, const adrp_r
                                      const float* boot_value, double gamma, float* rewards, uint8_t* valid, float* next_start,
                                      double* ep_return, int32_t* ep_length, void* stream) {
     RosterLearners who;
-    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_step", why);
-    if (const char* why = agents_error(io, agents)) return roster_err("adrp_race_roster_step", why);
-    if (!obs || !gate || !flags || !term || !trunc || !boot_value)
-        return roster_err("adrp_race_roster_step", "NULL argument (obs / gate / flags / term / trunc / boot_value)");
-    if (!rewards || !valid || !next_start || !ep_return || !ep_length)
-        return roster_err("adrp_race_roster_step", "NULL output (rewards / valid / next_start / ep_return / ep_length)");
+    if (const char* why = roster_error(io, &who)) return refuse("adrp_race_roster_step", why);
+    if (const char* why = agents_error(io, agents)) return refuse("adrp_race_roster_step", why);
+    if (const char* why = step_args_error(obs, gate, flags, term, trunc, boot_value, rewards, valid, next_start, ep_return, ep_length))
+        return refuse("adrp_race_roster_step", why);
     StreamDeviceGuard g((hipStream_t)stream);
     return step_launch(io, who, agents, obs, gate, flags, term, trunc, boot_value, gamma, rewards, valid, next_start, ep_return,
                        ep_length, (hipStream_t)stream);
@@ -133,9 +117,9 @@ extern "C" int adrp_race_roster_step(const adrp_race_roster_io* io, const adrp_r
 extern "C" int adrp_race_roster_done(const adrp_race_roster_io* io, const adrp_race_agents_io* agents, const uint8_t* term,
                                      const uint8_t* trunc, uint8_t* mask_out, void* stream) {
     RosterLearners who;
-    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_done", why);
-    if (const char* why = agents_error(io, agents)) return roster_err("adrp_race_roster_done", why);
-    if (!term || !trunc || !mask_out) return roster_err("adrp_race_roster_done", "NULL argument (term / trunc / mask_out)");
+    if (const char* why = roster_error(io, &who)) return refuse("adrp_race_roster_done", why);
+    if (const char* why = agents_error(io, agents)) return refuse("adrp_race_roster_done", why);
+    if (!term || !trunc || !mask_out) return refuse("adrp_race_roster_done", "NULL argument (term / trunc / mask_out)");
     StreamDeviceGuard g((hipStream_t)stream);
     hipLaunchKernelGGL(race_roster_done_kernel, dim3((io->num_envs + kRosterLanes - 1) / kRosterLanes), dim3(kRosterLanes), 0,
                        (hipStream_t)stream, io->num_envs, io->num_drones, who, io->num_learners, agents->alive, term, trunc,
@@ -148,19 +132,12 @@ extern "C" int adrp_race_roster_step_env(const adrp_race_roster_io* io, const ad
                                          double gamma, float* rewards, uint8_t* valid, float* next_start, double* ep_return,
                                          int32_t* ep_length, void* stream) {
     RosterLearners who;
-    if (const char* why = roster_error(io, &who)) return roster_err("adrp_race_roster_step_env", why);
-    if (const char* why = agents_error(io, agents)) return roster_err("adrp_race_roster_step_env", why);
-    if (!h) return roster_err("adrp_race_roster_step_env", "the handle is NULL");
-    if (h->cfg.task != ADRP_TASK_RACE) return roster_err("adrp_race_roster_step_env", "not a MultiRaceAviary handle");
-    if (h->E != agents->num_envs || h->N != agents->num_drones || h->D != agents->obs_dim)
-        return roster_err("adrp_race_roster_step_env", "the handle's E, N, D differ from the io's");
-    if (!obs || !term || !trunc || !boot_value)
-        return roster_err("adrp_race_roster_step_env", "NULL argument (obs / term / trunc / boot_value)");
-    if (!rewards || !valid || !next_start || !ep_return || !ep_length)
-        return roster_err("adrp_race_roster_step_env", "NULL output (rewards / valid / next_start / ep_return / ep_length)");
-    // the race state's int image: field k of drone slot e * N + n at ist[k * E * N + e * N + n] (RaceInt)
-    const size_t EN = size_t(h->E) * h->N;
+    if (const char* why = roster_error(io, &who)) return refuse("adrp_race_roster_step_env", why);
+    if (const char* why = agents_error(io, agents)) return refuse("adrp_race_roster_step_env", why);
+    if (const char* why = step_env_args_error(h, agents, obs, term, trunc, boot_value, rewards, valid, next_start, ep_return,
+                                              ep_length))
+        return refuse("adrp_race_roster_step_env", why);
     DeviceGuard g(h->device);
-    return step_launch(io, who, agents, obs, h->ist + size_t(RI_GATE) * EN, h->ist + size_t(RI_FLAGS) * EN, term, trunc, boot_value,
+    return step_launch(io, who, agents, obs, race_int_field(h, RI_GATE), race_int_field(h, RI_FLAGS), term, trunc, boot_value,
                        gamma, rewards, valid, next_start, ep_return, ep_length, (hipStream_t)stream);
 }

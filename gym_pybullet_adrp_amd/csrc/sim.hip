@@ -7,14 +7,11 @@
 
 #include <stdint.h>
 
-#include <string>
-
 #include "adrp_internal.h"
+#include "race_host_checks.h"
 #include "sim_kernel.h"
 
 namespace {
-
-int sim_err(const char* fn, const std::string& why) { return seterr(nullptr, ADRP_ERR_INVALID, std::string(fn) + ": " + why); }
 
 // returns nullptr when io is usable
 const char* ctrl_io_error(const adrp_race_ctrl_io* io) {
@@ -59,60 +56,51 @@ const char* wave_error(const adrp_race_results_io* io, int base, int n_open) {
     return nullptr;
 }
 
-int results_launch(const char* fn, const adrp_race_results_io* io, const int32_t* gate, const int32_t* flags,
+int results_launch(const adrp_race_results_io* io, const int32_t* gate, const int32_t* flags,
                    const float* rew, const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
     hipLaunchKernelGGL(race_results_kernel, dim3(1), dim3(kResLanes), 0, s, *io, gate, flags, rew, term, trunc);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(nullptr, ADRP_ERR_DEVICE, std::string(fn) + " launch: " + hipGetErrorString(e));
-    return ADRP_OK;
+    return launched("race results step");
 }
 
 }  // namespace
 
 extern "C" int adrp_race_controllers(const adrp_race_ctrl_io* io, double ep_time, void* stream) {
-    if (const char* why = ctrl_io_error(io)) return sim_err("adrp_race_controllers", why);
+    if (const char* why = ctrl_io_error(io)) return refuse("adrp_race_controllers", why);
     StreamDeviceGuard g((hipStream_t)stream);
     const int EN = io->num_envs * io->num_drones;
     hipLaunchKernelGGL(race_controller_kernel, dim3((EN + kCtrlLanes - 1) / kCtrlLanes), dim3(kCtrlLanes), 0,
                        (hipStream_t)stream, *io, ep_time);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(nullptr, ADRP_ERR_DEVICE, std::string("race controllers launch: ") + hipGetErrorString(e));
-    return ADRP_OK;
+    return launched("race controllers");
 }
 
 extern "C" int adrp_race_results_begin(adrp_race_results_io* io, int base, int n_open, void* stream) {
-    if (const char* why = results_io_error(io)) return sim_err("adrp_race_results_begin", why);
-    if (const char* why = wave_error(io, base, n_open)) return sim_err("adrp_race_results_begin", why);
+    if (const char* why = results_io_error(io)) return refuse("adrp_race_results_begin", why);
+    if (const char* why = wave_error(io, base, n_open)) return refuse("adrp_race_results_begin", why);
     io->base = base;
     StreamDeviceGuard g((hipStream_t)stream);
     hipLaunchKernelGGL(race_results_begin_kernel, dim3(1), dim3(kResLanes), 0, (hipStream_t)stream, *io, n_open);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return seterr(nullptr, ADRP_ERR_DEVICE, std::string("race results begin launch: ") + hipGetErrorString(e));
-    return ADRP_OK;
+    return launched("race results begin");
 }
 
 extern "C" int adrp_race_results_step(const adrp_race_results_io* io, const int32_t* gate, const int32_t* flags,
                                       const float* rew, const uint8_t* term, const uint8_t* trunc, void* stream) {
-    if (const char* why = results_io_error(io)) return sim_err("adrp_race_results_step", why);
-    if (const char* why = wave_error(io, io->base, 0)) return sim_err("adrp_race_results_step", why);
+    if (const char* why = results_io_error(io)) return refuse("adrp_race_results_step", why);
+    if (const char* why = wave_error(io, io->base, 0)) return refuse("adrp_race_results_step", why);
     if (!gate || !flags || !rew || !term || !trunc)
-        return sim_err("adrp_race_results_step", "NULL argument (gate / flags / rew / term / trunc)");
+        return refuse("adrp_race_results_step", "NULL argument (gate / flags / rew / term / trunc)");
     StreamDeviceGuard g((hipStream_t)stream);
-    return results_launch("race results step", io, gate, flags, rew, term, trunc, (hipStream_t)stream);
+    return results_launch(io, gate, flags, rew, term, trunc, (hipStream_t)stream);
 }
 
 extern "C" int adrp_race_results_step_env(const adrp_race_results_io* io, adrp_t* h, const float* rew, const uint8_t* term,
                                           const uint8_t* trunc, void* stream) {
-    if (const char* why = results_io_error(io)) return sim_err("adrp_race_results_step_env", why);
-    if (const char* why = wave_error(io, io->base, 0)) return sim_err("adrp_race_results_step_env", why);
-    if (!h) return sim_err("adrp_race_results_step_env", "the handle is NULL");
-    if (h->cfg.task != ADRP_TASK_RACE) return sim_err("adrp_race_results_step_env", "not a MultiRaceAviary handle");
+    if (const char* why = results_io_error(io)) return refuse("adrp_race_results_step_env", why);
+    if (const char* why = wave_error(io, io->base, 0)) return refuse("adrp_race_results_step_env", why);
+    if (!h) return refuse("adrp_race_results_step_env", "the handle is NULL");
+    if (h->cfg.task != ADRP_TASK_RACE) return refuse("adrp_race_results_step_env", "not a MultiRaceAviary handle");
     if (h->E != io->num_envs || h->N != io->num_drones)
-        return sim_err("adrp_race_results_step_env", "the handle's E, N differ from the io's");
-    if (!rew || !term || !trunc) return sim_err("adrp_race_results_step_env", "NULL argument (rew / term / trunc)");
-    // the race state's int image: field k of drone slot e * N + n at ist[k * E * N + e * N + n] (RaceInt)
-    const size_t EN = size_t(h->E) * h->N;
+        return refuse("adrp_race_results_step_env", "the handle's E, N differ from the io's");
+    if (!rew || !term || !trunc) return refuse("adrp_race_results_step_env", "NULL argument (rew / term / trunc)");
     DeviceGuard g(h->device);
-    return results_launch("race results step", io, h->ist + size_t(RI_GATE) * EN, h->ist + size_t(RI_FLAGS) * EN, rew, term,
-                          trunc, (hipStream_t)stream);
+    return results_launch(io, race_int_field(h, RI_GATE), race_int_field(h, RI_FLAGS), rew, term, trunc, (hipStream_t)stream);
 }

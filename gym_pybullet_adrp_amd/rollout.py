@@ -30,18 +30,99 @@ launch per step (csrc/agents_kernel.h).
 ``RosterRolloutCollector`` adds opponents to it: a roster gives every drone a role (the learner, the scripted
 ``HardCodedController``, a frozen policy, none), only the learner drones have buffer columns, and every drone is
 driven through the env's command path on its own env's episode clock (csrc/roster_kernel.h).
+
+The three are three classes with their own column layouts and step sequences.  What they have in common stands
+once: ``_Collector`` owns the ``n_steps`` x columns buffers, the sampling head of a step, and the tail of a rollout
+(the last values, ``adrp_gae``); ``_RaceAgentsCollector`` on top of it is the race part of the two per-drone
+collectors (their refusals, the validity and episode buffers, the ``adrp_race_agents_io`` over every drone slot).
+A roster's entries are parsed by ``controllers.entry_kinds``, which ``sim.ControllerBank`` shares.
 """
 import ctypes
 
 import torch
 
 from . import _lib
+from .controllers import entry_kinds, plan_commander, policies_act
 from .envs.multihover import MultiHoverAviary
 from .envs.race import MultiRaceAviary
+from .policy import MODES
 from .utils import abi
 
 
-class RolloutCollector:
+class _Collector:
+    """The ``n_steps`` x ``columns`` buffers of a collector (``T``, ``E``; one column per agent, ``D`` observation
+    floats each), the two pieces of ``_collect`` that do not depend on the column layout (``_sample_row``,
+    ``_finish``), and the plumbing around the library."""
+
+    def __init__(self, env, policy, n_steps, columns, D, gamma, gae_lambda, seed):
+        self.env, self.policy = env, policy
+        self.T, self.E = int(n_steps), int(columns)
+        self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
+        T, R, A = self.T, self.E, policy.act_dim
+        f32 = dict(dtype=torch.float32, device=env.device)
+        self.obs = torch.zeros((T, R, D), **f32)
+        self.actions = torch.zeros((T, R, A), **f32)
+        self.rewards, self.episode_starts, self.values, self.log_probs, self.advantages, self.returns = \
+            (torch.zeros((T, R), **f32) for _ in range(6))
+        self._last_start = torch.ones(R, **f32)         # SB3: _last_episode_starts = ones at reset
+        # _tv: value of the terminal observations; _scratch: the other outputs of a sampling launch made for its values
+        self.last_values, self.last_dones, self._tv = (torch.zeros(R, **f32) for _ in range(3))
+        self._scratch = (torch.zeros((R, 4 if policy.mode else A), **f32), torch.zeros((R, A), **f32), torch.zeros(R, **f32))
+        self.lib = _lib.load()
+        self.rollouts = 0
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise _lib.AdrpError(f"{what}: {self.lib.adrp_last_error(None).decode()}")
+
+    def _stream(self):
+        return _lib._raw_stream(self.obs.device.index)
+
+    def _values_of(self, obs2d, out):
+        """critic values of obs rows (the sampling launch; its action outputs go to scratch)"""
+        ea, a, lp = self._scratch
+        self.policy.sample(obs2d, self.seed, 0xFFFFFFFF, env_act=ea, action=a, value=out, log_prob=lp)
+
+    def collect(self):
+        """one rollout of n_steps env.steps -> fills the buffer and runs GAE over its columns (SB3 collect_rollouts +
+        compute_returns_and_advantage); every tensor stays on the device"""
+        # the env's device is the current one for the whole rollout: the launches take that device's
+        # current stream (a null stream is the current device's, ADVICE r4)
+        with torch.cuda.device(self.obs.device):
+            return self._collect()
+
+    def _sample_row(self, t, counter, env_act):
+        """the head of step t, once ``obs[t]`` is filled: the episode starts, and the policy sampled on the row (draw
+        ``counter``) into the buffer rows of t and into env_act"""
+        self.episode_starts[t].copy_(self._last_start)
+        self.policy.sample(self.obs[t], self.seed, counter, env_act=env_act, action=self.actions[t],
+                           value=self.values[t], log_prob=self.log_probs[t])
+
+    def _finish(self, last_obs):
+        """the tail of a rollout: values of the observations after the last step (SB3: policy.predict_values(new_obs)),
+        the last dones, GAE"""
+        self._values_of(last_obs, self.last_values)
+        self.last_dones.copy_(self._last_start)
+        rc = self.lib.adrp_gae(self.rewards.data_ptr(), self.values.data_ptr(), self.episode_starts.data_ptr(),
+                               self.last_values.data_ptr(), self.last_dones.data_ptr(), self.T, self.E, self.gamma,
+                               self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(), self._stream())
+        self._check(rc, "adrp_gae")
+        self.rollouts += 1
+        return self
+
+    def batches(self, batch_size, generator=None):
+        """RolloutBuffer.get(batch_size): shuffled minibatches of (obs, actions, old_values,
+        old_log_prob, advantages, returns) over the flattened n_steps x columns samples"""
+        n = self.T * self.E
+        idx = torch.randperm(n, device=self.obs.device, generator=generator)
+        flat = (self.obs.reshape(n, -1), self.actions.reshape(n, -1), self.values.reshape(n),
+                self.log_probs.reshape(n), self.advantages.reshape(n), self.returns.reshape(n))
+        for s in range(0, n, batch_size):
+            j = idx[s:s + batch_size]
+            yield tuple(x.index_select(0, j) for x in flat)
+
+
+class RolloutCollector(_Collector):
     """``n_steps`` x ``num_envs`` PPO rollout buffer on the env's device.
 
     policy: ``DevicePolicy`` with a critic (``set_critic`` / ``from_zip(critic=True)``), its input
@@ -70,59 +151,26 @@ class RolloutCollector:
             raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
         if episode_stats is not None and (episode_stats.E != env.num_envs or episode_stats.device != env.device):
             raise ValueError("episode_stats must hold num_envs envs on the env's device")
-        self.env, self.policy, self.episode_stats = env, policy, episode_stats
-        self.T, self.E = int(n_steps), env.num_envs
-        self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
+        super().__init__(env, policy, n_steps, env.num_envs, D, gamma, gae_lambda, seed)
+        self.episode_stats = episode_stats
         dev = env.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.obs = torch.zeros((self.T, self.E, D), **f32)
-        self.actions = torch.zeros((self.T, self.E, A), **f32)
-        self.rewards = torch.zeros((self.T, self.E), **f32)
-        self.episode_starts = torch.zeros((self.T, self.E), **f32)
-        self.values = torch.zeros((self.T, self.E), **f32)
-        self.log_probs = torch.zeros((self.T, self.E), **f32)
-        self.advantages = torch.zeros((self.T, self.E), **f32)
-        self.returns = torch.zeros((self.T, self.E), **f32)
-        self._env_act = torch.zeros((self.E,) + tuple(env._act_shape[1:]), **f32)
+        self._env_act = torch.zeros((self.E,) + tuple(env._act_shape[1:]), dtype=torch.float32, device=dev)
         self._term = torch.zeros((self.T, self.E), dtype=torch.bool, device=dev)
         self._trunc = torch.zeros((self.T, self.E), dtype=torch.bool, device=dev)
-        self._last_obs = torch.zeros((self.E, D), **f32)
-        self._last_start = torch.ones(self.E, **f32)         # SB3: _last_episode_starts = ones at reset
-        self.last_values = torch.zeros(self.E, **f32)
-        self.last_dones = torch.zeros(self.E, **f32)
-        # value of the terminal observations (scratch outputs of the sampling launch)
-        self._tv = torch.zeros(self.E, **f32)
-        self._scratch = (torch.zeros((self.E, 4 if policy.mode else A), **f32), torch.zeros((self.E, A), **f32),
-                         torch.zeros(self.E, **f32))
-        self.rollouts = 0
+        self._last_obs = torch.zeros((self.E, D), dtype=torch.float32, device=dev)
 
     def reset(self):
         obs, _ = self.env.reset()
         self._last_obs.copy_(obs.reshape(self.E, -1))
         self._last_start.fill_(1.0)
 
-    def _values_of(self, obs2d, out):
-        """critic values of obs rows (the sampling launch; its action outputs go to scratch)"""
-        ea, a, lp = self._scratch
-        self.policy.sample(obs2d, self.seed, 0xFFFFFFFF, env_act=ea, action=a, value=out, log_prob=lp)
-
-    def collect(self):
-        """one rollout of n_steps env.steps -> fills the buffer and runs GAE (SB3 collect_rollouts +
-        compute_returns_and_advantage); every tensor stays on the device"""
-        # the env's device is the current one for the whole rollout: the launches take that device's
-        # current stream (a null stream is the current device's, ADVICE r4)
-        with torch.cuda.device(self.obs.device):
-            return self._collect()
-
     def _collect(self):
-        env, pol, E, meter = self.env, self.policy, self.E, self.episode_stats
+        env, E, meter = self.env, self.E, self.episode_stats
         base = self.rollouts * self.T
         env_act = self._env_act.view(E, -1)
         for t in range(self.T):
             self.obs[t].copy_(self._last_obs)
-            self.episode_starts[t].copy_(self._last_start)
-            pol.sample(self.obs[t], self.seed, base + t, env_act=env_act, action=self.actions[t],
-                       value=self.values[t], log_prob=self.log_probs[t])
+            self._sample_row(t, base + t, env_act)
             obs, rew, term, trunc, info = env.step(self._env_act)
             self.rewards[t].copy_(rew)
             self._term[t].copy_(term)
@@ -137,31 +185,68 @@ class RolloutCollector:
             torch.where(boot, self.rewards[t] + self.gamma * self._tv, self.rewards[t], out=self.rewards[t])
             self._last_obs.copy_(obs.reshape(E, -1))
             self._last_start.copy_((term | trunc).to(torch.float32))
-        # values of the observations after the last step (SB3: policy.predict_values(new_obs))
-        self._values_of(self._last_obs, self.last_values)
-        self.last_dones.copy_(self._last_start)
-        rc = _lib.load().adrp_gae(self.rewards.data_ptr(), self.values.data_ptr(), self.episode_starts.data_ptr(),
-                                  self.last_values.data_ptr(), self.last_dones.data_ptr(), self.T, E, self.gamma,
-                                  self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(),
-                                  _lib._raw_stream(self.obs.device.index))
-        if rc != 0:
-            raise _lib.AdrpError(f"adrp_gae: {_lib.load().adrp_last_error(None).decode()}")
-        self.rollouts += 1
-        return self
-
-    def batches(self, batch_size, generator=None):
-        """RolloutBuffer.get(batch_size): shuffled minibatches of (obs, actions, old_values,
-        old_log_prob, advantages, returns) over the flattened n_steps x num_envs samples"""
-        n = self.T * self.E
-        idx = torch.randperm(n, device=self.obs.device, generator=generator)
-        flat = (self.obs.reshape(n, -1), self.actions.reshape(n, -1), self.values.reshape(n),
-                self.log_probs.reshape(n), self.advantages.reshape(n), self.returns.reshape(n))
-        for s in range(0, n, batch_size):
-            j = idx[s:s + batch_size]
-            yield tuple(x.index_select(0, j) for x in flat)
+        return self._finish(self._last_obs)
 
 
-class MultiAgentRolloutCollector:
+class _RaceAgentsCollector(_Collector):
+    """The race part of the two per-drone collectors, whatever their columns are: the refusals of an env or a policy
+    that cannot be collected from, the validity and agent-episode buffers of the columns, and the per-agent state of
+    all ``num_envs * N`` drone slots behind an ``adrp_race_agents_io`` (csrc/agents_kernel.h)."""
+
+    @staticmethod
+    def _refuse_env(env, who_is, who_needs):
+        if not isinstance(env, MultiRaceAviary):
+            raise ValueError(f"{who_is} collected from a MultiRaceAviary")
+        if env.cfg.autoreset:
+            raise ValueError(f"{who_needs} MultiRaceAviary(autoreset=False): the collector resets the finished envs "
+                             "itself, after the agents' step")
+
+    @staticmethod
+    def _refuse_policy(policy, D):
+        if not policy.has_critic:
+            raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
+        if policy.act_dim != 4:
+            raise ValueError("a race agent's policy emits the 4 FULLSTATE outputs (x, y, z, yaw)")
+        if policy.in_dim > D:
+            raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
+
+    def __init__(self, env, policy, n_steps, columns, gamma, gae_lambda, seed):
+        D = env.h.D
+        super().__init__(env, policy, n_steps, columns, D, gamma, gae_lambda, seed)
+        self.num_envs, self.N = env.num_envs, env.NUM_DRONES
+        T, R, S = self.T, self.E, self.num_envs * self.N
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=env.device)
+        self.valid = z((T, R), torch.uint8)
+        self.ep_return, self.ep_length = z((T, R), torch.float64), z((T, R), torch.int32)
+        self._mask = z(self.num_envs, torch.bool)
+        # per-agent state (adrp_race_agents_io): every drone slot, whether it has a column or not
+        self.wr_gate, self.run_length = z(S, torch.int32), z(S, torch.int32)
+        self.wr_target, self.wr_prev = z((S, 3), torch.float64), z((S, 3), torch.float64)
+        self.alive, self.run_return = z(S, torch.uint8), z(S, torch.float64)
+        io = abi.AdrpRaceAgentsIO()
+        io.struct_size = ctypes.sizeof(abi.AdrpRaceAgentsIO)
+        io.num_envs, io.num_drones, io.obs_dim, io.num_gates = self.num_envs, self.N, D, int(env.cfg.track.num_gates)
+        for k in ("wr_gate", "wr_target", "wr_prev", "alive", "run_return", "run_length"):
+            setattr(io, k, getattr(self, k).data_ptr())
+        self._io, self._ref = io, ctypes.byref(io)
+
+    def _agents_reset(self, obs, mask):
+        self._check(self.lib.adrp_race_agents_reset(self._ref, obs.data_ptr(), None if mask is None else mask.data_ptr(),
+                                                    self._stream()), "adrp_race_agents_reset")
+
+    def episode_summary(self):
+        """{"ep_rew_mean", "ep_len_mean", "episodes"} of the agent episodes that ended during the last rollout
+        (raw rewards, without the bootstrap): one host read, after the rollout; NaN means without an episode"""
+        ended = self.ep_length > 0
+        n = ended.sum()
+        ret = torch.where(ended, self.ep_return, torch.zeros_like(self.ep_return)).sum()
+        out = torch.stack((n.double(), ret, self.ep_length.sum().double())).cpu().tolist()
+        k = int(out[0])
+        return {"ep_rew_mean": out[1] / k if k else float("nan"), "ep_len_mean": out[2] / k if k else float("nan"),
+                "episodes": k}
+
+
+class MultiAgentRolloutCollector(_RaceAgentsCollector):
     """``n_steps`` x (``num_envs`` x ``NUM_DRONES``) PPO rollout buffer of a multi-drone race: column
     ``e * N + n`` is drone n of env e, every drone an agent of the one shared ``policy`` (its input the first
     ``policy.in_dim`` floats of the drone's own obs row, four outputs: the FULLSTATE setpoint).
@@ -180,61 +265,12 @@ class MultiAgentRolloutCollector:
     did not would need the dead rows' values zeroed before GAE (deviation 2)."""
 
     def __init__(self, env, policy, n_steps, gamma=0.99, gae_lambda=0.95, seed=0):
-        if not isinstance(env, MultiRaceAviary):
-            raise ValueError("per-drone agents are collected from a MultiRaceAviary")
-        if env.cfg.autoreset:
-            raise ValueError("per-drone agents need MultiRaceAviary(autoreset=False): the collector resets the finished "
-                             "envs itself, after the agents' step")
-        if not policy.has_critic:
-            raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
-        D, A = env.h.D, policy.act_dim
-        if A != 4:
-            raise ValueError("a race agent's policy emits the 4 FULLSTATE outputs (x, y, z, yaw)")
-        if policy.in_dim > D:
-            raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
-        self.env, self.policy = env, policy
-        self.num_envs, self.N = env.num_envs, env.NUM_DRONES
-        self.T, self.E = int(n_steps), self.num_envs * self.N
-        self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
-        dev = env.device
-        T, R = self.T, self.E
-        f32 = dict(dtype=torch.float32, device=dev)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.obs = torch.zeros((T, R, D), **f32)
-        self.actions = torch.zeros((T, R, A), **f32)
-        self.rewards, self.episode_starts, self.values, self.log_probs, self.advantages, self.returns = \
-            (torch.zeros((T, R), **f32) for _ in range(6))
-        self.valid = z((T, R), torch.uint8)
-        self.ep_return, self.ep_length = z((T, R), torch.float64), z((T, R), torch.int32)
+        self._refuse_env(env, "per-drone agents are", "per-drone agents need")
+        self._refuse_policy(policy, env.h.D)
+        super().__init__(env, policy, n_steps, env.num_envs * env.NUM_DRONES, gamma, gae_lambda, seed)
+        f32 = dict(dtype=torch.float32, device=env.device)
         self._env_act = torch.zeros((self.num_envs, self.N, 4), **f32)
-        self._last_obs = torch.zeros((R, D), **f32)
-        self._last_start = torch.ones(R, **f32)
-        self.last_values, self.last_dones, self._tv = (torch.zeros(R, **f32) for _ in range(3))
-        self._scratch = (torch.zeros((R, 4), **f32), torch.zeros((R, A), **f32), torch.zeros(R, **f32))
-        self._mask = z(self.num_envs, torch.bool)
-        # per-agent state (adrp_race_agents_io)
-        self.wr_gate, self.run_length = z(R, torch.int32), z(R, torch.int32)
-        self.wr_target, self.wr_prev = z((R, 3), torch.float64), z((R, 3), torch.float64)
-        self.alive, self.run_return = z(R, torch.uint8), z(R, torch.float64)
-        io = abi.AdrpRaceAgentsIO()
-        io.struct_size = ctypes.sizeof(abi.AdrpRaceAgentsIO)
-        io.num_envs, io.num_drones, io.obs_dim, io.num_gates = self.num_envs, self.N, D, int(env.cfg.track.num_gates)
-        for k in ("wr_gate", "wr_target", "wr_prev", "alive", "run_return", "run_length"):
-            setattr(io, k, getattr(self, k).data_ptr())
-        self._io, self._ref = io, ctypes.byref(io)
-        self.lib = _lib.load()
-        self.rollouts = 0
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise _lib.AdrpError(f"{what}: {self.lib.adrp_last_error(None).decode()}")
-
-    def _stream(self):
-        return _lib._raw_stream(self.obs.device.index)
-
-    def _agents_reset(self, obs, mask):
-        self._check(self.lib.adrp_race_agents_reset(self._ref, obs.data_ptr(), None if mask is None else mask.data_ptr(),
-                                                    self._stream()), "adrp_race_agents_reset")
+        self._last_obs = torch.zeros((self.E, env.h.D), **f32)
 
     def reset(self):
         with torch.cuda.device(self.obs.device):
@@ -243,27 +279,14 @@ class MultiAgentRolloutCollector:
             self._last_obs.copy_(obs.view(self.E, -1))
             self._last_start.fill_(1.0)
 
-    def _values_of(self, obs2d, out):
-        """critic values of obs rows (the sampling launch; its action outputs go to scratch)"""
-        ea, a, lp = self._scratch
-        self.policy.sample(obs2d, self.seed, 0xFFFFFFFF, env_act=ea, action=a, value=out, log_prob=lp)
-
-    def collect(self):
-        """one rollout of n_steps env.steps -> fills the buffer and runs GAE over the E N agent columns; every
-        tensor stays on the device"""
-        with torch.cuda.device(self.obs.device):
-            return self._collect()
-
     def _collect(self):
-        env, pol, R = self.env, self.policy, self.E
+        env, R = self.env, self.E
         base = self.rollouts * self.T
         env_act = self._env_act.view(R, 4)
         step_env = self.lib.adrp_race_agents_step_env
         for t in range(self.T):
             self.obs[t].copy_(self._last_obs)
-            self.episode_starts[t].copy_(self._last_start)
-            pol.sample(self.obs[t], self.seed, base + t, env_act=env_act, action=self.actions[t],
-                       value=self.values[t], log_prob=self.log_probs[t])
+            self._sample_row(t, base + t, env_act)
             obs, _, term, trunc, _ = env.step(self._env_act)
             # the bootstrap values: the critic on the post-step rows (read only where an alive drone's env
             # hit the time limit)
@@ -277,28 +300,10 @@ class MultiAgentRolloutCollector:
             obs, _ = env.reset(mask=mask)
             self._agents_reset(obs, mask)
             self._last_obs.copy_(obs.view(R, -1))
-        self._values_of(self._last_obs, self.last_values)
-        self.last_dones.copy_(self._last_start)
-        rc = self.lib.adrp_gae(self.rewards.data_ptr(), self.values.data_ptr(), self.episode_starts.data_ptr(),
-                               self.last_values.data_ptr(), self.last_dones.data_ptr(), self.T, R, self.gamma,
-                               self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(), self._stream())
-        self._check(rc, "adrp_gae")
-        self.rollouts += 1
-        return self
-
-    def episode_summary(self):
-        """{"ep_rew_mean", "ep_len_mean", "episodes"} of the agent episodes that ended during the last rollout
-        (raw rewards, without the bootstrap): one host read, after the rollout; NaN means without an episode"""
-        ended = self.ep_length > 0
-        n = ended.sum()
-        ret = torch.where(ended, self.ep_return, torch.zeros_like(self.ep_return)).sum()
-        out = torch.stack((n.double(), ret, self.ep_length.sum().double())).cpu().tolist()
-        k = int(out[0])
-        return {"ep_rew_mean": out[1] / k if k else float("nan"), "ep_len_mean": out[2] / k if k else float("nan"),
-                "episodes": k}
+        return self._finish(self._last_obs)
 
 
-class RosterRolloutCollector(MultiAgentRolloutCollector):
+class RosterRolloutCollector(_RaceAgentsCollector):
     """Per-drone PPO rollouts of a multi-drone race against opponents: ``roster`` gives every drone one role,
     ``"learner"`` (a sample of ``policy``, the one being trained), ``"hardcoded"`` (the scripted
     HardCodedController, delay = drone index as ``sim.ControllerBank``), a frozen ``DevicePolicy`` in mode
@@ -322,81 +327,29 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
     a scripted racer that flies its whole spline, the rows of a rollout are then almost all valid."""
 
     def __init__(self, env, policy, roster, n_steps, gamma=0.99, gae_lambda=0.95, seed=0, planner="host", end_on="env"):
-        from .policy import MODES, DevicePolicy
         if end_on not in ("env", "learners"):
             raise ValueError(f"end_on must be 'env' or 'learners', not {end_on!r}")
-        if not isinstance(env, MultiRaceAviary):
-            raise ValueError("a roster is collected from a MultiRaceAviary")
-        if env.cfg.autoreset:
-            raise ValueError("a roster needs MultiRaceAviary(autoreset=False): the collector resets the finished envs "
-                             "itself, after the agents' step")
+        self._refuse_env(env, "a roster is", "a roster needs")
         if not env.commands:
             raise ValueError("a roster needs MultiRaceAviary(commands=True): every drone is driven through the command path")
         if planner not in ("host", "device"):
             raise ValueError(f"planner must be 'host' or 'device', not {planner!r}")
-        if not policy.has_critic:
-            raise ValueError("the policy needs a critic (DevicePolicy.set_critic) to collect rollouts")
-        D, A = env.h.D, policy.act_dim
-        if A != 4:
-            raise ValueError("a race agent's policy emits the 4 FULLSTATE outputs (x, y, z, yaw)")
-        if policy.in_dim > D:
-            raise ValueError(f"the policy reads {policy.in_dim} inputs, the env's rows have {D}")
-        self.num_envs, self.N, self.end_on = env.num_envs, env.NUM_DRONES, end_on
+        self._refuse_policy(policy, env.h.D)
         roster = list(roster)
-        if len(roster) != self.N:
-            raise ValueError(f"the roster has {len(roster)} entries for {self.N} drones: give one per drone")
-        dev = env.device
-        self.roles, self.learners, self._frozen = [], [], []
-        for n, c in enumerate(roster):
-            if c is None or (isinstance(c, str) and c.lower() == "none"):
-                self.roles.append(abi.ROSTER_NONE)
-            elif isinstance(c, str) and c.lower() == "hardcoded":
-                self.roles.append(abi.ROSTER_HARDCODED)
-            elif isinstance(c, str) and c.lower() == "learner":
-                self.roles.append(abi.ROSTER_LEARNER)
-                self.learners.append(n)
-            elif isinstance(c, DevicePolicy):
-                if c.mode == MODES["raw"] or c.act_dim != 4:
-                    raise ValueError(f"drone {n}: a race policy emits a setpoint (mode 'relative' or 'absolute', 4 outputs)")
-                if c.in_dim > D:
-                    raise ValueError(f"drone {n}: the policy reads {c.in_dim} inputs, a drone's observation row has {D}")
-                if c.device != dev:
-                    raise ValueError(f"drone {n}: the policy lives on {c.device}, the env on {dev}")
-                self.roles.append(abi.ROSTER_POLICY)
-                self._frozen.append((n, c))
-            else:
-                raise ValueError(f"drone {n}: not a roster entry: {c!r} ('learner', 'hardcoded', a DevicePolicy or None)")
+        if len(roster) != env.NUM_DRONES:
+            raise ValueError(f"the roster has {len(roster)} entries for {env.NUM_DRONES} drones: give one per drone")
+        self.roles = entry_kinds(roster, env.h.D, env.device, "roster entry", learner=True)
+        self.learners = [n for n, r in enumerate(self.roles) if r == abi.ROSTER_LEARNER]
         if not self.learners:
             raise ValueError("the roster has no 'learner' drone: nothing to collect")
-        self.env, self.policy, self.roster, self.planner = env, policy, roster, planner
+        self._frozen = [(n, roster[n]) for n, r in enumerate(self.roles) if r == abi.ROSTER_POLICY]
         self.L = len(self.learners)
-        self.T, self.E = int(n_steps), self.L * self.num_envs
-        self.gamma, self.gae_lambda, self.seed = float(gamma), float(gae_lambda), int(seed)
-        T, R, E, N = self.T, self.E, self.num_envs, self.N
-        f32 = dict(dtype=torch.float32, device=dev)
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.obs = torch.zeros((T, R, D), **f32)
-        self.actions = torch.zeros((T, R, A), **f32)
-        self.rewards, self.episode_starts, self.values, self.log_probs, self.advantages, self.returns = \
-            (torch.zeros((T, R), **f32) for _ in range(6))
-        self.valid = z((T, R), torch.uint8)
-        self.ep_return, self.ep_length = z((T, R), torch.float64), z((T, R), torch.int32)
-        self._post = torch.zeros((R, D), **f32)            # the learner rows after the step, compact
-        self._last_start = torch.ones(R, **f32)
-        self.last_values, self.last_dones, self._tv = (torch.zeros(R, **f32) for _ in range(3))
-        self._scratch = (torch.zeros((R, 4), **f32), torch.zeros((R, A), **f32), torch.zeros(R, **f32))
-        self._mask = z(E, torch.bool)
-        # per-agent state (adrp_race_agents_io): all E N slots, the learner drones' are used
-        S = E * N
-        self.wr_gate, self.run_length = z(S, torch.int32), z(S, torch.int32)
-        self.wr_target, self.wr_prev = z((S, 3), torch.float64), z((S, 3), torch.float64)
-        self.alive, self.run_return = z(S, torch.uint8), z(S, torch.float64)
-        io = abi.AdrpRaceAgentsIO()
-        io.struct_size = ctypes.sizeof(abi.AdrpRaceAgentsIO)
-        io.num_envs, io.num_drones, io.obs_dim, io.num_gates = E, N, D, int(env.cfg.track.num_gates)
-        for k in ("wr_gate", "wr_target", "wr_prev", "alive", "run_return", "run_length"):
-            setattr(io, k, getattr(self, k).data_ptr())
-        self._io, self._ref = io, ctypes.byref(io)
+        super().__init__(env, policy, n_steps, self.L * env.num_envs, gamma, gae_lambda, seed)
+        self.roster, self.planner, self.end_on = roster, planner, end_on
+        R, E, N = self.E, self.num_envs, self.N
+        f32 = dict(dtype=torch.float32, device=env.device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=env.device)
+        self._post = torch.zeros((R, env.h.D), **f32)               # the learner rows after the step, compact
         # the roster (adrp_race_roster_io)
         self.clock = z(E, torch.int32)
         self.phase = z((3, E, N), torch.uint8)                      # took off, notified, landed
@@ -414,8 +367,6 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
         for k in ("clock", "phase", "setpoints", "learner_act", "codes", "args"):
             setattr(rio, k, getattr(self, k).data_ptr())
         self._rio, self._rref = rio, ctypes.byref(rio)
-        self.lib = _lib.load()
-        self.rollouts = 0
 
     @property
     def has_hardcoded(self):
@@ -424,7 +375,6 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
     def set_opponent(self, n, policy):
         """replace the frozen policy of drone ``n`` (a roster entry that was given as a ``DevicePolicy``), e.g. by a
         newer ``PPOLearner.snapshot()``; takes effect from the next step.  The caller closes the old one."""
-        from .policy import MODES
         if self.roles[n] != abi.ROSTER_POLICY:
             raise ValueError(f"drone {n} is not a frozen-policy drone of this roster")
         if policy.mode == MODES["raw"] or policy.act_dim != 4 or policy.in_dim > self.env.h.D or policy.device != self.env.device:
@@ -449,21 +399,14 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
         with torch.cuda.device(self.obs.device):
             obs, _ = self.env.reset()
             if self.has_hardcoded:
-                from .hardcoded import HardCodedCommander
-                if self.commander is None:
-                    self.commander = HardCodedCommander(obs, device=self.env.device, planner=self.planner)
-                    ref, off = self.commander.reference_trajectory, self.commander._offset
-                    assert off.dtype == torch.int64 and off.is_contiguous() and ref.is_contiguous()
-                    self._rio.ref_len, self._rio.ref, self._rio.offset = self.commander.L, ref.data_ptr(), off.data_ptr()
-                else:
-                    self.commander.replan(obs)
+                self.commander = plan_commander(self.commander, self._rio, obs, self.env.device, self.planner)
             self._agents_reset(obs, None)
             self._tick(None)
             self._last_start.fill_(1.0)
             self._env_obs = obs
 
     def _collect(self):
-        env, pol, R, E, N, D = self.env, self.policy, self.E, self.num_envs, self.N, self.env.h.D
+        env, R = self.env, self.E
         if getattr(self, "_env_obs", None) is None:
             raise RuntimeError("RosterRolloutCollector.reset() first: the scripted drones plan from the reset observation")
         lib, base = self.lib, self.rollouts * self.T
@@ -472,13 +415,8 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
         cmd = (self.codes, self.args)
         for t in range(self.T):
             self._gather(self.obs[t], obs)
-            self.episode_starts[t].copy_(self._last_start)
-            pol.sample(self.obs[t], self.seed, base + t, env_act=env_act, action=self.actions[t],
-                       value=self.values[t], log_prob=self.log_probs[t])
-            for n, p in self._frozen:
-                # drone n's rows in place: row e at obs + (e * N + n) * D, so base + n * D with stride N * D
-                self._check(lib.adrp_policy_act(p.h, obs.data_ptr() + 4 * n * D, E, N * D, p.mode,
-                                                self.setpoints[n].data_ptr(), self._stream()), "adrp_policy_act")
+            self._sample_row(t, base + t, env_act)
+            policies_act(lib, self._frozen, obs, self.setpoints, self._stream())
             self._check(lib.adrp_race_roster_act(self._rref, self._stream()), "adrp_race_roster_act")
             obs, _, term, trunc, _ = env.step(cmd)
             # the bootstrap values: the critic on the learner drones' post-step rows
@@ -499,11 +437,4 @@ class RosterRolloutCollector(MultiAgentRolloutCollector):
             self._tick(mask)
         self._env_obs = obs
         self._gather(self._post, obs)
-        self._values_of(self._post, self.last_values)
-        self.last_dones.copy_(self._last_start)
-        rc = lib.adrp_gae(self.rewards.data_ptr(), self.values.data_ptr(), self.episode_starts.data_ptr(),
-                          self.last_values.data_ptr(), self.last_dones.data_ptr(), self.T, R, self.gamma,
-                          self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(), self._stream())
-        self._check(rc, "adrp_gae")
-        self.rollouts += 1
-        return self
+        return self._finish(self._post)

@@ -31,6 +31,7 @@ import torch
 
 from . import _lib
 from .commands import CMD_ARGS
+from .controllers import entry_kinds, plan_commander, policies_act
 from .policy import MODES, DevicePolicy
 from .utils import abi
 from .utils.enums import Physics, RaceMode
@@ -71,22 +72,7 @@ class ControllerBank:
         self.E, self.N, self.D = int(env.num_envs), int(env.NUM_DRONES), int(env.h.D)
         self.device = env.device
         self.controllers = _expand(controllers, self.N)
-        self.kinds = []
-        for n, c in enumerate(self.controllers):
-            if c is None or (isinstance(c, str) and c.lower() == "none"):
-                self.kinds.append(abi.RACE_CTRL_NONE)
-            elif isinstance(c, str) and c.lower() == "hardcoded":
-                self.kinds.append(abi.RACE_CTRL_HARDCODED)
-            elif isinstance(c, DevicePolicy):
-                if c.mode == MODES["raw"] or c.act_dim != 4:
-                    raise ValueError(f"drone {n}: a race policy emits a setpoint (mode 'relative' or 'absolute', 4 outputs)")
-                if c.in_dim > self.D:
-                    raise ValueError(f"drone {n}: the policy reads {c.in_dim} inputs, a drone's observation row has {self.D}")
-                if c.device != self.device:
-                    raise ValueError(f"drone {n}: the policy lives on {c.device}, the env on {self.device}")
-                self.kinds.append(abi.RACE_CTRL_POLICY)
-            else:
-                raise ValueError(f"drone {n}: not a controller: {c!r} ('hardcoded', a DevicePolicy or None)")
+        self.kinds = entry_kinds(self.controllers, self.D, self.device, "controller")
         E, N = self.E, self.N
         self.codes = torch.zeros((E, N), dtype=torch.int32, device=self.device)
         self.args = torch.zeros((E, N, CMD_ARGS), dtype=torch.float64, device=self.device)
@@ -111,16 +97,7 @@ class ControllerBank:
         """fresh controllers from the reset observation (scripts/sim.py:72-76): the scripted drones re-plan, every
         phase flag is cleared"""
         if self.has_hardcoded:
-            from .hardcoded import HardCodedCommander
-            if self.commander is None:
-                self.commander = HardCodedCommander(obs0, delay=delay, device=self.device, planner=self.planner)
-                self._io.ref_len = self.commander.L
-                self._io.ref = self.commander.reference_trajectory.data_ptr()
-                self._io.offset = self.commander._offset.data_ptr()
-                assert self.commander._offset.dtype == torch.int64 and self.commander._offset.is_contiguous()
-                assert self.commander.reference_trajectory.is_contiguous()
-            else:
-                self.commander.replan(obs0)
+            self.commander = plan_commander(self.commander, self._io, obs0, self.device, self.planner, delay=delay)
         self.phase.zero_()
 
     def predict(self, obs, ep_time):
@@ -133,13 +110,7 @@ class ControllerBank:
             if not (obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous()
                     and tuple(obs.shape) == (self.E, self.N, self.D) and obs.device == self.device):
                 raise ValueError(f"obs must be a contiguous float32 [{self.E}, {self.N}, {self.D}] tensor on {self.device}")
-            base = obs.data_ptr()
-            for n, pol in self._policies:
-                # drone n's rows in place: row e at obs + (e * N + n) * D, so base + n * D with stride N * D
-                rc = self.lib.adrp_policy_act(pol.h, base + 4 * n * self.D, self.E, self.N * self.D, pol.mode,
-                                              self.setpoints[n].data_ptr(), stream)
-                if rc != 0:
-                    raise _lib.AdrpError(f"adrp_policy_act: {self.lib.adrp_last_error(None).decode()}")
+            policies_act(self.lib, self._policies, obs, self.setpoints, stream)
         rc = self.lib.adrp_race_controllers(self._ref, float(ep_time), stream)
         if rc != 0:
             raise _lib.AdrpError(self.lib.adrp_last_error(None).decode())

@@ -92,13 +92,12 @@ class TorchAgents:
 
 def run_arm(col, arm, steps, torch_agents):
     """`steps` collector steps of one arm (buffer row t % T)"""
-    env, pol, R = col.env, col.policy, col.E
+    env, R = col.env, col.E
     env_act = col._env_act.view(R, 4)
     for k in range(steps):
         t = k % col.T
         col.obs[t].copy_(col._last_obs)
-        col.episode_starts[t].copy_(col._last_start)
-        pol.sample(col.obs[t], col.seed, k, env_act=env_act, action=col.actions[t], value=col.values[t], log_prob=col.log_probs[t])
+        col._sample_row(t, k, env_act)
         obs, _, term, trunc, _ = env.step(col._env_act)
         col._values_of(obs.view(R, -1), col._tv)
         if arm == "fused":

@@ -59,13 +59,12 @@ class Pieces:
 
     def collect(self):
         col = self.col
-        env, pol, E, N, cm = col.env, col.policy, col.num_envs, col.N, col.commander
+        env, E, N, cm = col.env, col.num_envs, col.N, col.commander
         obs, base = col._env_obs, col.rollouts * col.T
         env_act = col.learner_act.view(E, 4)
         for t in range(col.T):
             col.obs[t].copy_(obs[:, 0])
-            col.episode_starts[t].copy_(col._last_start)
-            pol.sample(col.obs[t], col.seed, base + t, env_act=env_act, action=col.actions[t], value=col.values[t], log_prob=col.log_probs[t])
+            col._sample_row(t, base + t, env_act)
             ep_time = self.clock / float(env.CTRL_FREQ)
             codes, args = cm.predict(ep_time)
             codes[:, 0] = self.fullstate
@@ -94,12 +93,7 @@ class Pieces:
             cm._flags &= ~col._mask[None, :, None]
         col._env_obs = obs
         col._post.copy_(obs[:, 0])
-        col._values_of(col._post, col.last_values)
-        col.last_dones.copy_(col._last_start)
-        col._check(col.lib.adrp_gae(col.rewards.data_ptr(), col.values.data_ptr(), col.episode_starts.data_ptr(),
-                                    col.last_values.data_ptr(), col.last_dones.data_ptr(), col.T, E, col.gamma, col.gae_lambda,
-                                    col.advantages.data_ptr(), col.returns.data_ptr(), col._stream()), "adrp_gae")
-        col.rollouts += 1
+        col._finish(col._post)
 
 
 def main():
